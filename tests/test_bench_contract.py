@@ -26,17 +26,28 @@ def test_default_and_driver_command_lines_name_the_declared_c3():
     assert (a.gpus, a.steps, a.warmup) == (1, 5, 1)  # no flags: one GPU, a handful of steps
     assert a.runs == mod.DECLARED_RUNS == 1_000_000_000 and a.sigma == 253 and a.reads == 10_000_000
     assert (a.read_len, a.bp_per_read, a.out_bits, a.scaling) == (44, 200, 16, "weak")
+    # a plain run times the headline and nothing else: every leg, the CPU baseline and the other scaling wait for --full
+    assert not a.full and a.dump_outputs is None
+    assert a.no_extras and a.no_cpu_baseline and a.no_other_scaling
+    assert not any(a.want(leg) for leg in ("host_path", "dna_m200", "c4_ms_doc", "long_reads_c5", "shard_1of8",
+                                           "real_bwt_digest_walk", "cli_file_to_file", "real_bwt_large"))
+    mod, a = _bench(["--legs", "c4_ms_doc"])
+    assert not a.want("c4_ms_doc")
+    mod, a = _bench(["--full"])
     assert a.want("dna_m200") and a.want("c4_ms_doc") and a.want("long_reads_c5") and a.want("real_bwt_digest_walk")
     assert a.want("cli_file_to_file") and not a.want("real_bwt_large")  # (the large real BWT is opt-in: minutes of suffix sorting)
+    assert not a.no_cpu_baseline and not a.no_other_scaling
     assert 0 < a.cpu_seconds <= 5 and a.wall_budget > 240
     mod, a = _bench(["--gpus", "8", "--steps", "20", "--warmup", "5"])  # the driver's line
     assert (a.gpus, a.steps, a.warmup, a.runs) == (8, 20, 5, 1_000_000_000)
-    mod, a = _bench(["--stand-in", "--no-extras", "--scaling", "strong"])
+    mod, a = _bench(["--full", "--stand-in", "--no-extras", "--scaling", "strong"])
     assert a.runs == 1 << 28 and not a.want("dna_m200") and a.scaling == "strong"
-    mod, a = _bench(["--legs", "positive_100,c4_ms_doc"])
+    mod, a = _bench(["--full", "--legs", "positive_100,c4_ms_doc"])
     assert a.want("c4_ms_doc") and a.want("positive_100") and not a.want("dna_m200")
-    mod, a = _bench(["--legs", "real_bwt_large"])
+    mod, a = _bench(["--full", "--legs", "real_bwt_large"])
     assert a.want("real_bwt_large") and not a.want("cli_file_to_file")
+    mod, a = _bench(["--steps", "7", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.dump_outputs == "out" and not a.full
 
 
 def test_bytes_per_step_is_survey_8d():

@@ -13,7 +13,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--runs", "1500000", "--reads", "200000", "--steps", "2", "--no-cpu-baseline", "--no-extras"]
+# (--full: the line carries the other scaling beside its own; no legs, no CPU baseline)
+COMMON = ["--runs", "1500000", "--reads", "200000", "--steps", "2", "--full", "--no-cpu-baseline", "--no-extras"]
 
 
 def _bench(args, share=False):

@@ -6,7 +6,7 @@
 LEGS=${AB_LEGS:-positive_100,positive_0}
 for rep in $(seq 1 ${AB_REPS:-3}); do
   for lib in spumoni_amd/libspumoni_gpu*.so; do
-    SPUMONI_GPU_LIB=$PWD/$lib timeout 600 python bench.py --no-cpu-baseline --legs "$LEGS" "$@" 2>/tmp/ab.err | tail -1 | \
+    SPUMONI_GPU_LIB=$PWD/$lib timeout 600 python bench.py --full --no-cpu-baseline --legs "$LEGS" "$@" 2>/tmp/ab.err | tail -1 | \
       python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

@@ -6,7 +6,7 @@ for pass in 1 2; do
   if [ $pass = 1 ]; then C="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY";
   else C="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES"; fi
   rm -rf /tmp/pmc$pass
-  timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d /tmp/pmc$pass -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --legs c4_ms_doc "$@" > /tmp/pmc$pass.log 2>&1 || tail -5 /tmp/pmc$pass.log
+  timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d /tmp/pmc$pass -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --legs c4_ms_doc "$@" > /tmp/pmc$pass.log 2>&1 || tail -5 /tmp/pmc$pass.log
   f=$(find /tmp/pmc$pass -name "*counter_collection.csv" | head -1)
   python - "$f" <<PY
 import csv, sys, collections, re

@@ -2,7 +2,7 @@
 # (gpurun_out/c5_trace.txt: start_us dur_us kernel).  RUNS / READS as for bench.py.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/c5t; mkdir -p gpurun_out
-rocprofv3 --kernel-trace --output-format csv -d /tmp/c5t -- python bench.py --no-cpu-baseline --legs long_reads_c5 ${RUNS:+--runs $RUNS} --reads ${READS:-100000} 2>/dev/null | tail -1 | python -c "
+rocprofv3 --kernel-trace --output-format csv -d /tmp/c5t -- python bench.py --full --no-cpu-baseline --legs long_reads_c5 ${RUNS:+--runs $RUNS} --reads ${READS:-100000} 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())['long_reads_c5']; print({k:v for k,v in d.items() if k!='what'})"
 f=$(find /tmp/c5t -name "*kernel_trace.csv" | head -1)

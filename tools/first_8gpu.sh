@@ -34,7 +34,7 @@ python -c "import __graft_entry__ as g; g.build()" > "$out/build.log" 2>&1
 # ---- the bench: weak and strong scaling in one line per N (other_scaling) ----
 for n in 1 2 4 8; do
   [ "$n" -le "$ngpu" ] || continue
-  timeout 1800 python bench.py --gpus $n --steps 20 --warmup 3 --no-extras > "$out/bench_n$n.json" 2> "$out/bench_n$n.log"
+  timeout 1800 python bench.py --gpus $n --steps 20 --warmup 3 --full --no-extras > "$out/bench_n$n.json" 2> "$out/bench_n$n.log"
   python - "$out/bench_n$n.json" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 try:
