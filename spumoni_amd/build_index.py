@@ -22,8 +22,9 @@ It writes exactly the files `spumoni run` (ours) consumes, under `<prefix>.fa*`:
 The text is each sequence followed by its reverse complement, no separators, upper-cased (the order
 src/refbuilder.cpp:100-180 writes them in); the BWT / thresholds / samples are computed here by suffix sorting, not by
 PFP, and nothing here has been compared with an upstream-built index (none exists offline).
-The suffix array is built by prefix doubling on the GPU when one is present (torch), else on
-the CPU; the null statistics are computed with the HIP path itself.
+The index is built by the HIP builder (include/spumoni_build.h) when the library has it and a device
+to run it on, else by the torch prefix doubling of synth.index_from_text (the same arrays); the null statistics are
+computed with the HIP path itself.
 """
 from __future__ import annotations
 
@@ -246,6 +247,20 @@ def write_doc_array(path, doc_start, doc_end, ndocs):
         f.write(_int_vector(doc_end, w))
 
 
+def hip_builder_available() -> bool:
+    """The library offers the HIP builder and has a device to run it on (decided by the platform, not by an option)."""
+    L = capi.lib()
+    return hasattr(L, "spb_build_from_text") and L.spx_device_count() > 0
+
+
+def build_raw_index(text, doc_lengths):
+    """The raw index of `text`: the HIP builder where the platform has it, else the torch suffix sort (the same arrays)."""
+    if hip_builder_available():
+        return capi.build_raw(text, doc_lengths=doc_lengths)
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    return synth.index_from_text(torch.from_numpy(text).to(dev), doc_lengths=doc_lengths).cpu()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m spumoni_amd.build_index")
     ap.add_argument("-r", "--ref", help="single FASTA file")
@@ -312,8 +327,7 @@ def main(argv=None):
     text = np.concatenate(parts)
     if text.min() < 2:
         sys.exit("the text contains bytes 0/1, which are reserved for the terminator")
-    dev = "cuda" if torch.cuda.is_available() else "cpu"
-    raw = synth.index_from_text(torch.from_numpy(text).to(dev), doc_lengths=doc_lengths).cpu()
+    raw = build_raw_index(text, doc_lengths)
     prefix = a.output + (".bin" if a.minimizer_alphabet else ".fa")  # src/spumoni.cpp:744-747
     os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
     with open(prefix, "wb") as f:

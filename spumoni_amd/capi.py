@@ -503,3 +503,66 @@ def pad_seqs(seqs):
     padded = torch.zeros(((n + 3) // 4) * 4 + 32, dtype=torch.uint8, device=seqs.device)
     padded[:n] = seqs
     return padded
+
+
+# ---- the index builder (include/spumoni_build.h) -------------------------------------------------------------------
+_SPB_READY = False
+
+
+def _spb() -> C.CDLL:
+    """The library with the spb_* argtypes set (on first use: a library without the builder still loads for queries)."""
+    global _SPB_READY
+    L = lib()
+    if not hasattr(L, "spb_build_from_text"):
+        raise SpxError(f"{LIB_PATH} has no index builder (spb_build_from_text): there is no CPU fallback for the HIP path")
+    if not _SPB_READY:
+        vp, u64 = C.c_void_p, C.c_uint64
+        L.spb_build_from_text.restype = vp
+        L.spb_build_from_text.argtypes = [vp, u64, vp, C.c_uint32, C.c_int, C.c_int]
+        L.spb_build_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.spb_build_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.spb_build_free.argtypes = [vp]
+        _SPB_READY = True
+    return L
+
+
+def build_raw(text, doc_lengths=None, with_samples: bool = True, device: int = 0):
+    """The run-length BWT, thresholds and SA samples of `text` (bytes >= 2, no terminator) built on the device:
+    a synth.RawIndex of CPU tensors, field for field what synth.index_from_text(text, doc_lengths, with_samples) gives
+    (document ids only when doc_lengths is given and with_samples)."""
+    import torch
+
+    from . import synth
+
+    if isinstance(text, torch.Tensor):
+        t = text.detach().to("cpu", torch.uint8).contiguous().numpy()
+    else:
+        t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else
+                                 np.asarray(text, dtype=np.uint8))
+    L = _spb()
+    dl = None if doc_lengths is None else np.ascontiguousarray(np.asarray(list(doc_lengths), dtype=np.uint64))
+    h = L.spb_build_from_text(_np_ptr(t), t.size, _np_ptr(dl), 0 if dl is None else dl.size, 1 if with_samples else 0,
+                              device)
+    if not h:
+        raise SpxError(L.spx_last_error().decode())
+    try:
+        n, r = C.c_uint64(), C.c_uint64()
+        _check(L.spb_build_stats(h, C.byref(n), C.byref(r)))
+        r = r.value
+        heads = np.empty(r, dtype=np.uint8)
+        lens, thr = np.empty(r, dtype=np.int64), np.empty(r, dtype=np.int64)
+        ssa = esa = ds = de = None
+        if with_samples:
+            ssa, esa = np.empty(r, dtype=np.int64), np.empty(r, dtype=np.int64)
+            if dl is not None:
+                ds, de = np.empty(r, dtype=np.int64), np.empty(r, dtype=np.int64)
+        _check(L.spb_build_copy(h, _np_ptr(heads), _np_ptr(lens), _np_ptr(thr), _np_ptr(ssa), _np_ptr(esa),
+                                _np_ptr(ds), _np_ptr(de)))
+    finally:
+        L.spb_build_free(h)
+
+    def tt(a):
+        return None if a is None else torch.from_numpy(a)
+
+    return synth.RawIndex(heads=tt(heads), lens=tt(lens), thr=tt(thr), n=n.value, ssa=tt(ssa), esa=tt(esa),
+                          doc_start=tt(ds), doc_end=tt(de), text=torch.from_numpy(t.copy()))

@@ -42,7 +42,7 @@ static int usable_devices() {
     return n;
 }
 
-static int select_device(int device) {
+int select_device(int device) {
     const int n = usable_devices();
     if (n <= 0) {
         set_error("no HIP device visible: libspumoni_gpu has no CPU fallback");

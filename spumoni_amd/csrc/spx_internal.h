@@ -14,6 +14,8 @@ namespace spx {
 
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
+// hipSetDevice(device) after checking that it exists and is a gfx950 (SPX_E_NODEVICE: no usable device)
+int select_device(int device);
 
 #define SPX_HIP(call)                                                        \
     do {                                                                     \
