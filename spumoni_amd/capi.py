@@ -566,3 +566,50 @@ def build_raw(text, doc_lengths=None, with_samples: bool = True, device: int = 0
 
     return synth.RawIndex(heads=tt(heads), lens=tt(lens), thr=tt(thr), n=n.value, ssa=tt(ssa), esa=tt(esa),
                           doc_start=tt(ds), doc_end=tt(de), text=torch.from_numpy(t.copy()))
+
+
+# ---- reference text preparation (include/spumoni_reftext.h) -------------------------------------------------------
+REFTEXT_EXPORTS = ["spr_text_from_fasta", "spr_text_stats", "spr_text_copy", "spr_text_free"]
+_SPR_READY = False
+
+
+def _spr() -> C.CDLL:
+    """The library with the spr_* argtypes set (on first use)."""
+    global _SPR_READY
+    L = lib()
+    if not hasattr(L, "spr_text_from_fasta"):
+        raise SpxError(f"{LIB_PATH} has no text preparation (spr_text_from_fasta): there is no CPU fallback")
+    if not _SPR_READY:
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.spr_text_from_fasta.restype = vp
+        L.spr_text_from_fasta.argtypes = [vp, u64, vp, u32, C.c_int, C.c_int, u32, u32, u64, C.c_int]
+        L.spr_text_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.spr_text_copy.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.spr_text_free.argtypes = [vp]
+        _SPR_READY = True
+    return L
+
+
+def prepare_fasta(files, rev_comp: bool = True, digest_kind: int = 0, k: int = 4, w: int = 11, max_text: int = 0,
+                  device: int = 0):
+    """The text `spumoni build` indexes from FASTA file contents (a list of bytes, already inflated), prepared on the
+    device: a dict with "text", "file_text_lengths", "fwd" (the sequences, case preserved, back to back), "seq_ends"
+    and "seq_file" (numpy arrays)."""
+    data = np.frombuffer(b"".join(files), dtype=np.uint8)
+    ends = np.ascontiguousarray(np.cumsum([len(f) for f in files]), dtype=np.uint64)
+    L = _spr()
+    h = L.spr_text_from_fasta(_np_ptr(data) if data.size else None, data.size, _np_ptr(ends), ends.size,
+                              1 if rev_comp else 0, digest_kind, k, w, max_text, device)
+    if not h:
+        raise SpxError(L.spx_last_error().decode())
+    try:
+        nt, ns, nf = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(L.spr_text_stats(h, C.byref(nt), C.byref(ns), C.byref(nf)))
+        out = {"text": np.empty(nt.value, dtype=np.uint8), "file_text_lengths": np.empty(ends.size, dtype=np.uint64),
+               "fwd": np.empty(nf.value, dtype=np.uint8), "seq_ends": np.empty(ns.value, dtype=np.uint64),
+               "seq_file": np.empty(ns.value, dtype=np.uint32)}
+        _check(L.spr_text_copy(h, *[_np_ptr(out[x]) for x in ("text", "file_text_lengths", "fwd", "seq_ends",
+                                                                "seq_file")]))
+    finally:
+        L.spr_text_free(h)
+    return out

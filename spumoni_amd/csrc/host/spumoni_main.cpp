@@ -387,6 +387,8 @@ static int dump_sdsl_main(int argc, char** argv) {
     return 0;
 }
 
+int build_main(int argc, char** argv);  // build_main.cpp
+
 static int spumoni_usage() {
     std::fprintf(stderr, "SPUMONI has different sub-commands to run which can used as follows:\n");
     std::fprintf(stderr, "Usage: spumoni <command> [options]\n\n");
@@ -402,9 +404,7 @@ int main(int argc, char** argv) {
     if (argc > 3 && std::strcmp(argv[1], "dump-sdsl") == 0) return dump_sdsl_main(argc - 1, argv + 1);
     std::fprintf(stderr, "\n\033[1m\033[31mSPUMONI version: %s \033[0m\n\n", SPUMONI_VERSION);
     if (argc > 1) {
-        if (std::strcmp(argv[1], "build") == 0)
-            fatal_error("`spumoni build` is not part of the MI355X run-path package: build the index with the\n"
-                        "       reference (keep the raw files with -k) and query it here.");
+        if (std::strcmp(argv[1], "build") == 0) return build_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "run") == 0) {
             const int rc = run_main(argc - 1, argv + 1);
             if (std::getenv("SPX_FREE_TRACE")) std::fprintf(stderr, "[spumoni] main returns %d\n", rc);

@@ -632,6 +632,178 @@ __global__ void __launch_bounds__(64) k_digest_chunks(const DigestArgs a, const 
     }
 }
 
+// ---- long reads with characters outside ACGT: a wavefront per WCHUNK characters -------------------------------------
+// A flagged read (a chromosome with runs of N) is cut into items of WCHUNK characters, each digested by one wavefront as
+// k_digest_wave digests a read, but emitting only for the k-mers that end inside the item.  The k-mer stream skips every
+// k-mer with a character outside ACGT, so the halo is counted in k-mers, not characters: an item starts at hs, the start
+// of the wsz-th valid k-mer that ends before the item (or at the read's start), so that the window of its first k-mer and
+// the one before it lie wholly in what the wavefront has seen.  hs comes from the items' counts of valid k-mer ends
+// (k_wchunk_valid_ends), walked back item by item and then byte by byte inside the item where the count is reached.
+// Items' emit counts, one scan, and every item writes at its read's offset plus the emits of the read's items before it.
+constexpr uint32_t WCHUNK = 4096;
+
+struct WaveChunks {
+    const uint64_t* w_start;  // item g: first character (input offset)
+    const uint32_t* w_rd;     // read (0xffffffff: an empty entry up to the bound)
+    uint64_t* w_hs;           // where its wavefront starts (halo)
+    uint32_t* vk;             // valid k-mer ends inside it
+    const uint64_t* wfirst;   // per read: its first item
+    uint64_t* w_cnt;          // pass 0: w_cnt[g + 1] = emits; after the inclusive scan w_cnt[g] = emits of the items before g
+    const uint64_t* rd_out;   // pass 1: the reads' offsets in the output
+    uint64_t bound;
+};
+
+__global__ void k_wchunk_count(const uint64_t* offs, uint64_t nreads, uint64_t* cnt) {
+    const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
+    if (q > nreads) return;
+    cnt[q] = q < nreads ? (offs[q + 1] - offs[q] + WCHUNK - 1) / WCHUNK : 0;
+}
+
+__global__ void k_wchunk_fill(const uint64_t* offs, uint64_t nreads, const uint64_t* first, uint64_t bound, uint64_t* w_start,
+                              uint32_t* w_rd) {
+    const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
+    if (q < nreads) {
+        const uint64_t b = offs[q], e = offs[q + 1];
+        uint64_t g = first[q];
+        for (uint64_t at = b; at < e; at += WCHUNK, ++g) {
+            w_start[g] = at;
+            w_rd[g] = (uint32_t)q;
+        }
+    }
+    for (uint64_t g = first[nreads] + q; g <= bound; g += (uint64_t)gridDim.x * 256) {
+        w_start[g] = offs[nreads];
+        w_rd[g] = 0xffffffffu;
+    }
+}
+
+// the k-mer ending at p (k characters of the read, all ACGT)
+__device__ __forceinline__ bool valid_end(const uint8_t* seqs, uint64_t rbeg, uint64_t p, uint32_t k) {
+    if (p + 1 < rbeg + k) return false;
+    for (uint32_t j = 0; j < k; ++j)
+        if (base_code(seqs[p - j]) > 3) return false;
+    return true;
+}
+
+__global__ void __launch_bounds__(64) k_wchunk_valid_ends(const DigestArgs a, const WaveChunks w) {
+    for (uint64_t g = blockIdx.x; g < w.bound; g += gridDim.x) {
+        const uint32_t rd = w.w_rd[g];
+        if (rd == 0xffffffffu || a.only[rd] == 0) continue;
+        const uint64_t rbeg = a.offs[rd], rend = a.offs[rd + 1];
+        const uint64_t cs = w.w_start[g], ce = cs + WCHUNK < rend ? cs + WCHUNK : rend;
+        uint32_t n = 0;
+        for (uint64_t p0 = cs; p0 < ce; p0 += 64) {
+            const uint64_t p = p0 + threadIdx.x;
+            n += (uint32_t)__popcll(__ballot(p < ce && valid_end(a.seqs, rbeg, p, a.k)));
+        }
+        if (threadIdx.x == 0) w.vk[g] = n;
+    }
+}
+
+__global__ void k_wchunk_halo(const DigestArgs a, const WaveChunks w) {
+    const uint64_t g = blockIdx.x * 256ull + threadIdx.x;
+    if (g >= w.bound) return;
+    const uint32_t rd = w.w_rd[g];
+    const uint64_t cs = w.w_start[g];
+    if (rd == 0xffffffffu || a.only[rd] == 0 || w.vk[g] == 0) {  // (no k-mer ends here: nothing to emit, no halo)
+        w.w_hs[g] = cs;
+        return;
+    }
+    const uint64_t rbeg = a.offs[rd], first = w.wfirst[rd];
+    uint64_t hs = rbeg, acc = 0;
+    for (uint64_t i = g; i-- > first;) {
+        if (acc + w.vk[i] < a.wsz) {
+            acc += w.vk[i];
+            continue;
+        }
+        for (uint64_t p = w.w_start[i + 1]; p-- > w.w_start[i];) {
+            if (valid_end(a.seqs, rbeg, p, a.k) && ++acc == a.wsz) {
+                hs = p + 1 - a.k;
+                break;
+            }
+        }
+        break;
+    }
+    w.w_hs[g] = hs;
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(64) k_digest_wave_chunks(const DigestArgs a, const WaveChunks w) {
+    extern __shared__ uint8_t lds[];
+    uint8_t* const keys = lds;
+    uint8_t* const mins = lds + a.ring;
+    uint8_t* const lut = lds + 2 * a.ring;
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = lane; i < 256; i += 64) lut[i] = a.key_of_kmer[i];
+    __syncthreads();
+    const uint32_t rmask = a.ring - 1;
+    const uint32_t k = a.k, wsz = a.wsz;
+    const uint64_t lt = (1ull << lane) - 1;
+    const uint64_t mult = a.kind == SPX_DIGEST_DNA ? k : 1;
+    for (uint64_t g = blockIdx.x; g < w.bound; g += gridDim.x) {
+        const uint32_t rd = w.w_rd[g];
+        if (rd == 0xffffffffu || a.only[rd] == 0) {
+            if (PASS == 0 && lane == 0) w.w_cnt[g + 1] = 0;
+            continue;
+        }
+        const uint64_t rend = a.offs[rd + 1];
+        const uint64_t cs = w.w_start[g], ce = cs + WCHUNK < rend ? cs + WCHUNK : rend;
+        const uint64_t base = w.w_hs[g];
+        const uint64_t len = ce - base, from = cs - base;  // local positions from `from` on are the item's
+        uint64_t ob = 0;
+        if (PASS == 1) ob = w.rd_out[rd] + (w.w_cnt[g] - w.w_cnt[w.wfirst[rd]]) * mult;
+        uint64_t t_base = 0, e_base = 0, prev_valid = 0;
+        uint32_t prev_code = 0;
+        for (uint64_t p0 = 0; p0 < len; p0 += 64) {
+            const uint64_t p = p0 + lane;
+            const uint32_t code = p < len ? (uint32_t)base_code(a.seqs[base + p]) : 4u;
+            const uint64_t valid = __ballot(code < 4);
+            uint64_t kv = valid;
+            uint32_t kmer = code & 3;
+            for (uint32_t j = 1; j < k; ++j) {
+                kv &= (valid << j) | (prev_valid >> (64 - j));
+                const uint32_t up = __shfl_up(code, j), carry = __shfl(prev_code, (int)(64 + lane - j) & 63);
+                kmer |= ((lane >= j ? up : carry) & 3) << (2 * j);
+            }
+            const bool has = (kv >> lane) & 1;
+            const uint64_t t = t_base + __popcll(kv & lt);
+            if (has) keys[t & rmask] = lut[kmer];
+            __syncthreads();
+            const bool reports = has && t + 1 >= wsz;
+            uint32_t mn = 0xffffffffu;
+            if (reports) {
+                for (uint32_t j = 0; j < wsz; ++j) mn = min(mn, (uint32_t)keys[(t - j) & rmask]);
+                mins[t & rmask] = (uint8_t)mn;
+            }
+            __syncthreads();
+            const bool emit = reports && p >= from && (t + 1 == wsz || mins[(t - 1) & rmask] != mn);
+            const uint64_t em = __ballot(emit);
+            if (PASS == 1 && emit) {
+                const uint64_t e = e_base + __popcll(em & lt);
+                if (a.kind == SPX_DIGEST_PROMOTED) {
+                    a.out[ob + e] = (uint8_t)(mn > 2 ? mn : mn + 3);
+                } else {
+                    const uint32_t code_min = mn ^ a.xm;
+                    for (uint32_t j = 0; j < k; ++j)
+                        a.out[ob + e * k + j] = (uint8_t)letter_of((code_min >> (2 * (k - 1 - j))) & 3);
+                }
+            }
+            t_base += __popcll(kv);
+            e_base += __popcll(em);
+            prev_valid = valid;
+            prev_code = code;
+            __syncthreads();
+        }
+        if (PASS == 0 && lane == 0) w.w_cnt[g + 1] = e_base;
+    }
+}
+
+// a flagged read's byte count: the emits of its items
+__global__ void k_wchunk_read_counts(const uint32_t* bad, const uint64_t* wfirst, const uint64_t* w_cnt, uint64_t nreads,
+                                     uint64_t mult, uint64_t* rcount) {
+    const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
+    if (q < nreads && bad[q]) rcount[q + 1] = (w_cnt[wfirst[q + 1]] - w_cnt[wfirst[q]]) * mult;
+}
+
 // a flagged read (a character outside ACGT) is the wavefront-per-read kernel's: its bytes count in its first chunk
 __global__ void k_dchunk_fix_counts(const uint32_t* c_rd, const uint64_t* first_chunk, const uint32_t* bad, const uint64_t* read_count,
                                     uint64_t bound, uint64_t* c_count) {
@@ -912,13 +1084,36 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
         else
             k_digest_chunks<SPX_DIGEST_DNA><<<gridc, 64, 0, st>>>(a, c_start, c_rd, bound, c_count, bad);
         SPX_HIP(hipGetLastError());
-        // the reads with a character outside ACGT: counted by the wavefront-per-read kernel (it returns at once for the others)
+        // the reads with a character outside ACGT: counted by a wavefront per WCHUNK characters (k_digest_wave_chunks; every
+        // kernel returns at once for the other reads)
         const size_t lds = 2 * (size_t)ring + 256;
-        const uint32_t gridw = (uint32_t)(nreads < cus * 64 ? nreads : cus * 64);
         DigestArgs aw = a;
         aw.only = bad;
         aw.counts = rcount;
-        k_digest_wave<0><<<gridw, 64, lds, st>>>(aw);
+        const uint64_t wb = total_chars / WCHUNK + nreads + 1;
+        uint64_t *wfirst = nullptr, *w_start = nullptr, *w_hs = nullptr, *w_cnt = nullptr;
+        uint32_t *w_rd = nullptr, *vk = nullptr;
+        SPX_HIP(scr.get((void**)&wfirst, (nreads + 2) * 8));
+        SPX_HIP(scr.get((void**)&w_start, (wb + 2) * 8));
+        SPX_HIP(scr.get((void**)&w_rd, (wb + 2) * 4));
+        SPX_HIP(scr.get((void**)&w_hs, (wb + 2) * 8));
+        SPX_HIP(scr.get((void**)&vk, (wb + 2) * 4));
+        SPX_HIP(scr.get((void**)&w_cnt, (wb + 2) * 8));
+        WaveChunks wc{w_start, w_rd, w_hs, vk, wfirst, w_cnt, d_out_offs, wb};
+        const unsigned gw = (unsigned)((wb + 255) / 256);
+        k_wchunk_count<<<gq, 256, 0, st>>>(d_offs, nreads, wfirst);
+        rc = scan(wfirst, nreads + 1, false);
+        if (rc != SPX_OK) return rc;
+        k_wchunk_fill<<<gq, 256, 0, st>>>(d_offs, nreads, wfirst, wb, w_start, w_rd);
+        const uint32_t gridw = (uint32_t)(wb < cus * 64 ? wb : cus * 64);
+        k_wchunk_valid_ends<<<gridw, 64, 0, st>>>(aw, wc);
+        k_wchunk_halo<<<gw, 256, 0, st>>>(aw, wc);
+        SPX_HIP(hipMemsetAsync(w_cnt, 0, 8, st));
+        k_digest_wave_chunks<0><<<gridw, 64, lds, st>>>(aw, wc);
+        SPX_HIP(hipGetLastError());
+        rc = scan(w_cnt, wb + 1, true);
+        if (rc != SPX_OK) return rc;
+        k_wchunk_read_counts<<<gq, 256, 0, st>>>(bad, wfirst, w_cnt, nreads, kind == SPX_DIGEST_DNA ? k : 1, rcount);
         k_dchunk_fix_counts<<<gc, 256, 0, st>>>(c_rd, first_chunk, bad, rcount, bound, c_count);
         rc = scan(c_count, bound + 1, true);  // c_count[g]: where chunk g's bytes go in the concatenated output
         if (rc != SPX_OK) return rc;
@@ -935,7 +1130,7 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
             k_digest_unstash<SPX_DIGEST_DNA><<<grid2, 64, 0, st>>>(au, stash);
         aw.out_offs = d_out_offs;
         aw.out = d_out;
-        k_digest_wave<1><<<gridw, 64, lds, st>>>(aw);
+        k_digest_wave_chunks<1><<<gridw, 64, lds, st>>>(aw, wc);
         SPX_HIP(hipGetLastError());
         k_zero_tail<<<1, 64, 0, st>>>(d_out_offs, nreads, d_out);
         SPX_HIP(hipGetLastError());

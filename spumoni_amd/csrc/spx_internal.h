@@ -170,7 +170,7 @@ struct spx_index {
     // that two handles on one device -- the CLI's two workers per device -- overlap one's copies with the other's kernels
     hipStream_t ctx_stream = nullptr;
     // the digestion's scratch (spx_digest.hip: grow-only, under mu), the stream its last call ran on and what that call enqueued
-    static constexpr int NDIGSCR = 9;
+    static constexpr int NDIGSCR = 15;
     hipEvent_t ev_dig = nullptr;
     hipStream_t dig_stream = nullptr;
     bool dig_used = false;
