@@ -218,7 +218,6 @@ static int own_arrays_alone(spx_index* ix) {
 // counters, events and knobs every index carries, however its arrays came to be
 static int init_runtime(spx_index* ix) {
     default_charhash(ix->charhash);
-    if (const char* e = getenv("SPX_WAVES_PER_CU")) ix->waves_per_cu = atoi(e);  // experiment knob
     SPX_HIP(hipMalloc((void**)&ix->counters, sizeof(WalkCounters)));
     SPX_HIP(hipMemset(ix->counters, 0, sizeof(WalkCounters)));
     SPX_HIP(hipEventCreate(&ix->ev0));
@@ -951,14 +950,13 @@ static int run_pipelined(spx_index* ix, int mode, const uint8_t* seqs, const uin
     // walk is faster than either copy) plus whatever passes before the first result can leave: so the first piece is
     // small (1/64 of the reads: copied in, walked and on its way out after ~0.4 ms instead of the ~3.7 ms an eighth of
     // the batch and the whole offsets array took), and every piece is 1.5 x the one before -- less than the 1.7 x by
-    // which the walk outruns the copy-out, so the copy-out stream never waits for a walk.  SPX_PIPE_EVEN=1: equal pieces.
+    // which the walk outruns the copy-out, so the copy-out stream never waits for a walk.
     uint64_t cut[NCH + 1];
     {
-        static const bool even = getenv("SPX_PIPE_EVEN") != nullptr;
         double acc = 0, piece = 1.0 / 64.0;
         cut[0] = 0;
         for (int c = 0; c < NCH; ++c) {
-            acc += even ? 1.0 / NCH : piece;
+            acc += piece;
             piece *= 1.5;
             // (the series reaches the whole before the last piece: what is left then is one smaller piece)
             cut[c + 1] = (c + 1 == NCH || acc >= 1.0) ? nreads : (uint64_t)((double)nreads * acc);

@@ -44,7 +44,7 @@ struct DigestArgs {
     uint32_t tile;   // lane-per-read kernel: bytes of input staged in LDS at a time
     uint32_t tpack;  // -m: the four character hashes T[A] | T[C] << 8 | T[G] << 16 | T[T] << 24
     uint8_t key_of_kmer[256];  // sort key of every k-mer code: the hash (-m) or code ^ xm (-a)
-    const uint32_t* only;      // k_digest_wave: digest only the reads whose flag is set (null: all of them)
+    const uint32_t* only;      // the wave-chunk kernels: digest only the reads whose flag is set
     uint64_t* counts;          // pass 0: counts[q + 1] = bytes read q digests to
     const uint64_t* out_offs;  // pass 1
     uint8_t* out;
@@ -57,72 +57,78 @@ __device__ __forceinline__ int base_code(uint32_t c) {
     return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
 }
 
+// One wavefront digests the characters [base, base + len) as one k-mer stream, 64 positions per iteration, and emits only
+// for the positions from `from` on (the ones before are a halo that fills the window).  Pass 0 counts the emits, pass 1
+// writes them from out[ob] on.  lds: the ring of stream keys, the ring of window minima (by stream index), the key table.
 template <int PASS>
-__global__ void __launch_bounds__(64) k_digest_wave(const DigestArgs a) {
-    extern __shared__ uint8_t lds[];
-    uint8_t* const keys = lds;            // ring of stream keys
-    uint8_t* const mins = lds + a.ring;   // ring of window minima, by stream index
-    uint8_t* const lut = lds + 2 * a.ring;
+__device__ __forceinline__ uint64_t wave_digest(const DigestArgs& a, uint8_t* lds, uint64_t base, uint64_t len, uint64_t from,
+                                                uint64_t ob) {
+    uint8_t* const keys = lds;
+    uint8_t* const mins = lds + a.ring;
+    const uint8_t* const lut = lds + 2 * a.ring;
     const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) lut[i] = a.key_of_kmer[i];
-    __syncthreads();
     const uint32_t rmask = a.ring - 1;
     const uint32_t k = a.k, wsz = a.wsz;
     const uint64_t lt = (1ull << lane) - 1;
-    for (uint64_t rd = blockIdx.x; rd < a.nreads; rd += gridDim.x) {
-        if (a.only != nullptr && a.only[rd] == 0) continue;
-        const uint64_t base = a.offs[rd];
-        const uint64_t len = a.offs[rd + 1] - base;
-        uint64_t ob = 0;
-        if (PASS == 1) ob = a.out_offs[rd];
-        uint64_t t_base = 0;  // k-mers streamed so far
-        uint64_t e_base = 0;  // values emitted so far
-        uint64_t prev_valid = 0;
-        uint32_t prev_code = 0;
-        for (uint64_t p0 = 0; p0 < len; p0 += 64) {
-            const uint64_t p = p0 + lane;
-            const uint32_t code = p < len ? (uint32_t)base_code(a.seqs[base + p]) : 4u;
-            const uint64_t valid = __ballot(code < 4);
-            // k-mer ending at p: the k characters p-k+1 .. p must all be ACGT
-            uint64_t kv = valid;
-            uint32_t kmer = code & 3;
-            for (uint32_t j = 1; j < k; ++j) {
-                kv &= (valid << j) | (prev_valid >> (64 - j));
-                const uint32_t up = __shfl_up(code, j), carry = __shfl(prev_code, (int)(64 + lane - j) & 63);
-                kmer |= ((lane >= j ? up : carry) & 3) << (2 * j);
-            }
-            const bool has = (kv >> lane) & 1;
-            const uint64_t t = t_base + __popcll(kv & lt);
-            if (has) keys[t & rmask] = lut[kmer];
-            __syncthreads();
-            const bool reports = has && t + 1 >= wsz;
-            uint32_t mn = 0xffffffffu;
-            if (reports) {
-                for (uint32_t j = 0; j < wsz; ++j) mn = min(mn, (uint32_t)keys[(t - j) & rmask]);
-                mins[t & rmask] = (uint8_t)mn;
-            }
-            __syncthreads();
-            // mseq_vec.empty() || mseq_vec.back() != x   (values are < 256: the uint8_t vector
-            // compares exactly)
-            const bool emit = reports && (t + 1 == wsz || mins[(t - 1) & rmask] != mn);
-            const uint64_t em = __ballot(emit);
-            if (PASS == 1 && emit) {
-                const uint64_t e = e_base + __popcll(em & lt);
-                if (a.kind == SPX_DIGEST_PROMOTED) {
-                    a.out[ob + e] = (uint8_t)(mn > 2 ? mn : mn + 3);
-                } else {
-                    const uint32_t code_min = mn ^ a.xm;
-                    for (uint32_t j = 0; j < k; ++j)
-                        a.out[ob + e * k + j] = (uint8_t)letter_of((code_min >> (2 * (k - 1 - j))) & 3);
-                }
-            }
-            t_base += __popcll(kv);
-            e_base += __popcll(em);
-            prev_valid = valid;
-            prev_code = code;
-            __syncthreads();
+    uint64_t t_base = 0;  // k-mers streamed so far
+    uint64_t e_base = 0;  // values emitted so far
+    uint64_t prev_valid = 0;
+    uint32_t prev_code = 0;
+    for (uint64_t p0 = 0; p0 < len; p0 += 64) {
+        const uint64_t p = p0 + lane;
+        const uint32_t code = p < len ? (uint32_t)base_code(a.seqs[base + p]) : 4u;
+        const uint64_t valid = __ballot(code < 4);
+        // k-mer ending at p: the k characters p-k+1 .. p must all be ACGT
+        uint64_t kv = valid;
+        uint32_t kmer = code & 3;
+        for (uint32_t j = 1; j < k; ++j) {
+            kv &= (valid << j) | (prev_valid >> (64 - j));
+            const uint32_t up = __shfl_up(code, j), carry = __shfl(prev_code, (int)(64 + lane - j) & 63);
+            kmer |= ((lane >= j ? up : carry) & 3) << (2 * j);
         }
-        if (PASS == 0 && lane == 0) a.counts[rd + 1] = e_base * (a.kind == SPX_DIGEST_DNA ? k : 1);
+        const bool has = (kv >> lane) & 1;
+        const uint64_t t = t_base + __popcll(kv & lt);
+        if (has) keys[t & rmask] = lut[kmer];
+        __syncthreads();
+        const bool reports = has && t + 1 >= wsz;
+        uint32_t mn = 0xffffffffu;
+        if (reports) {
+            for (uint32_t j = 0; j < wsz; ++j) mn = min(mn, (uint32_t)keys[(t - j) & rmask]);
+            mins[t & rmask] = (uint8_t)mn;
+        }
+        __syncthreads();
+        // mseq_vec.empty() || mseq_vec.back() != x   (values are < 256: the uint8_t vector
+        // compares exactly)
+        const bool emit = reports && p >= from && (t + 1 == wsz || mins[(t - 1) & rmask] != mn);
+        const uint64_t em = __ballot(emit);
+        if (PASS == 1 && emit) {
+            const uint64_t e = e_base + __popcll(em & lt);
+            if (a.kind == SPX_DIGEST_PROMOTED) {
+                a.out[ob + e] = (uint8_t)(mn > 2 ? mn : mn + 3);
+            } else {
+                const uint32_t code_min = mn ^ a.xm;
+                for (uint32_t j = 0; j < k; ++j)
+                    a.out[ob + e * k + j] = (uint8_t)letter_of((code_min >> (2 * (k - 1 - j))) & 3);
+            }
+        }
+        t_base += __popcll(kv);
+        e_base += __popcll(em);
+        prev_valid = valid;
+        prev_code = code;
+        __syncthreads();
+    }
+    return e_base;
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(64) k_digest_wave(const DigestArgs a) {
+    extern __shared__ uint8_t lds[];
+    for (uint32_t i = threadIdx.x; i < 256; i += 64) lds[2 * a.ring + i] = a.key_of_kmer[i];
+    __syncthreads();
+    for (uint64_t rd = blockIdx.x; rd < a.nreads; rd += gridDim.x) {
+        const uint64_t base = a.offs[rd];
+        const uint64_t e = wave_digest<PASS>(a, lds, base, a.offs[rd + 1] - base, 0, PASS == 1 ? a.out_offs[rd] : 0);
+        if (PASS == 0 && threadIdx.x == 0) a.counts[rd + 1] = e * (a.kind == SPX_DIGEST_DNA ? a.k : 1);
     }
 }
 
@@ -169,9 +175,6 @@ struct SwarState {
 
 __device__ __forceinline__ uint32_t promote4(uint32_t m) {  // x > 2 ? x : x + 3 on four bytes (src/spumoni.cpp:311)
     const uint32_t ge3 = (m | ((m | 0x80808080u) - 0x03030303u)) & 0x80808080u;
-#ifdef SPX_EXP_NOPROMOTE
-    return m;
-#endif
     const uint32_t lt = (ge3 ^ 0x80808080u) >> 7;  // 1 in every byte below 3
     return m + lt + (lt << 1);
 }
@@ -216,15 +219,7 @@ __global__ void __launch_bounds__(64) k_digest_lanes(const DigestArgs a) {
     auto rot4 = [](uint32_t v, uint32_t r) {
         return r ? (((v << r) & (0x01010101u * ((0xffu << r) & 0xffu))) | ((v >> (8 - r)) & (0x01010101u * (0xffu >> (8 - r))))) : v;
     };
-#ifdef SPX_EXP_TABV
-    uint32_t T0 = a.tpack, R1 = rot4(a.tpack, 1), R2 = rot4(a.tpack, 2), R3 = rot4(a.tpack, 3);
-    asm volatile("v_mov_b32 %0, %0" : "+v"(T0));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(R1));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(R2));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(R3));
-#else
     const uint32_t T0 = a.tpack, R1 = rot4(a.tpack, 1), R2 = rot4(a.tpack, 2), R3 = rot4(a.tpack, 3);
-#endif
     const uint32_t xm4 = (a.xm & 0xffu) * 0x01010101u;
     constexpr uint32_t FIRST = 10;  // the first reporting position of a read: k - 1 + wsz - 1
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
@@ -303,11 +298,7 @@ __global__ void __launch_bounds__(64) k_digest_lanes(const DigestArgs a) {
                                    t3 = __builtin_amdgcn_alignbyte(t, q.tp, 1);
                     q.tp = t;
                     uint32_t key;
-#ifdef SPX_EXP_DNAKEY
-                    if (false)
-#else
                     if (KIND == SPX_DIGEST_PROMOTED)
-#endif
                         key = __builtin_amdgcn_perm(T0, T0, t) ^ __builtin_amdgcn_perm(R1, R1, t1) ^
                               __builtin_amdgcn_perm(R2, R2, t2) ^ __builtin_amdgcn_perm(R3, R3, t3);
                     else
@@ -345,9 +336,6 @@ __global__ void __launch_bounds__(64) k_digest_lanes(const DigestArgs a) {
                     nacc += (uint32_t)__popc(idx);
                     if (nacc >= 4) {
                         const uint32_t w4 = KIND == SPX_DIGEST_PROMOTED ? promote4((uint32_t)acc) : (uint32_t)acc;
-#ifdef SPX_EXP_DIGEST_NOSTORE
-                        if (w4 == 0x12345678u)
-#endif
                         __builtin_memcpy(a.out + ob + e, &w4, 4);
                         acc >>= 32;
                         nacc -= 4;
@@ -478,30 +466,33 @@ __global__ void __launch_bounds__(64) k_digest_lanes(const DigestArgs a) {
 // reads.  A read with a character outside ACGT is flagged and redone by the wavefront-per-read kernel afterwards.
 constexpr uint32_t DCHUNK = 240, DHALO = 12;
 
-__global__ void k_dchunk_count(const uint64_t* offs, uint64_t nreads, uint64_t* cnt, uint32_t* bad) {
+// Reads cut into pieces of LEN characters (k_digest_chunks' chunks, k_digest_wave_chunks' items).  Count: cnt[q] = pieces
+// of read q (exclusive scan: cnt[nreads] = pieces in all).
+template <uint32_t LEN>
+__global__ void k_split_count(const uint64_t* offs, uint64_t nreads, uint64_t* cnt) {
     const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
     if (q > nreads) return;
-    cnt[q] = q < nreads ? (offs[q + 1] - offs[q] + DCHUNK - 1) / DCHUNK : 0;  // (exclusive scan: cnt[nreads] = chunks in all)
-    if (q < nreads) bad[q] = 0;
+    cnt[q] = q < nreads ? (offs[q + 1] - offs[q] + LEN - 1) / LEN : 0;
 }
 
-// chunk g: input offset c_start[g], read c_rd[g]; entries from the batch's last chunk up to `bound` are empty chunks at the
+// piece g: input offset start[g], read rd[g]; entries from the batch's last piece up to `bound` are empty pieces at the
 // input's end (the launches are sized by the bound: nothing returns to the host)
-__global__ void k_dchunk_fill(const uint64_t* offs, uint64_t nreads, const uint64_t* first_chunk, uint64_t bound, uint64_t* c_start,
-                              uint32_t* c_rd) {
+template <uint32_t LEN>
+__global__ void k_split_fill(const uint64_t* offs, uint64_t nreads, const uint64_t* first, uint64_t bound, uint64_t* start,
+                             uint32_t* rd) {
     const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
     if (q < nreads) {
         const uint64_t b = offs[q], e = offs[q + 1];
-        uint64_t g = first_chunk[q];
-        for (uint64_t at = b; at < e; at += DCHUNK, ++g) {
-            c_start[g] = at;
-            c_rd[g] = (uint32_t)q;
+        uint64_t g = first[q];
+        for (uint64_t at = b; at < e; at += LEN, ++g) {
+            start[g] = at;
+            rd[g] = (uint32_t)q;
         }
     }
     // (the entries between the count and the bound: every thread takes its share)
-    for (uint64_t g = first_chunk[nreads] + q; g <= bound; g += (uint64_t)gridDim.x * 256) {
-        c_start[g] = offs[nreads];
-        c_rd[g] = 0xffffffffu;
+    for (uint64_t g = first[nreads] + q; g <= bound; g += (uint64_t)gridDim.x * 256) {
+        start[g] = offs[nreads];
+        rd[g] = 0xffffffffu;
     }
 }
 
@@ -653,29 +644,6 @@ struct WaveChunks {
     uint64_t bound;
 };
 
-__global__ void k_wchunk_count(const uint64_t* offs, uint64_t nreads, uint64_t* cnt) {
-    const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
-    if (q > nreads) return;
-    cnt[q] = q < nreads ? (offs[q + 1] - offs[q] + WCHUNK - 1) / WCHUNK : 0;
-}
-
-__global__ void k_wchunk_fill(const uint64_t* offs, uint64_t nreads, const uint64_t* first, uint64_t bound, uint64_t* w_start,
-                              uint32_t* w_rd) {
-    const uint64_t q = blockIdx.x * 256ull + threadIdx.x;
-    if (q < nreads) {
-        const uint64_t b = offs[q], e = offs[q + 1];
-        uint64_t g = first[q];
-        for (uint64_t at = b; at < e; at += WCHUNK, ++g) {
-            w_start[g] = at;
-            w_rd[g] = (uint32_t)q;
-        }
-    }
-    for (uint64_t g = first[nreads] + q; g <= bound; g += (uint64_t)gridDim.x * 256) {
-        w_start[g] = offs[nreads];
-        w_rd[g] = 0xffffffffu;
-    }
-}
-
 // the k-mer ending at p (k characters of the read, all ACGT)
 __device__ __forceinline__ bool valid_end(const uint8_t* seqs, uint64_t rbeg, uint64_t p, uint32_t k) {
     if (p + 1 < rbeg + k) return false;
@@ -729,71 +697,21 @@ __global__ void k_wchunk_halo(const DigestArgs a, const WaveChunks w) {
 template <int PASS>
 __global__ void __launch_bounds__(64) k_digest_wave_chunks(const DigestArgs a, const WaveChunks w) {
     extern __shared__ uint8_t lds[];
-    uint8_t* const keys = lds;
-    uint8_t* const mins = lds + a.ring;
-    uint8_t* const lut = lds + 2 * a.ring;
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) lut[i] = a.key_of_kmer[i];
+    for (uint32_t i = threadIdx.x; i < 256; i += 64) lds[2 * a.ring + i] = a.key_of_kmer[i];
     __syncthreads();
-    const uint32_t rmask = a.ring - 1;
-    const uint32_t k = a.k, wsz = a.wsz;
-    const uint64_t lt = (1ull << lane) - 1;
-    const uint64_t mult = a.kind == SPX_DIGEST_DNA ? k : 1;
+    const uint64_t mult = a.kind == SPX_DIGEST_DNA ? a.k : 1;
     for (uint64_t g = blockIdx.x; g < w.bound; g += gridDim.x) {
         const uint32_t rd = w.w_rd[g];
         if (rd == 0xffffffffu || a.only[rd] == 0) {
-            if (PASS == 0 && lane == 0) w.w_cnt[g + 1] = 0;
+            if (PASS == 0 && threadIdx.x == 0) w.w_cnt[g + 1] = 0;
             continue;
         }
         const uint64_t rend = a.offs[rd + 1];
         const uint64_t cs = w.w_start[g], ce = cs + WCHUNK < rend ? cs + WCHUNK : rend;
-        const uint64_t base = w.w_hs[g];
-        const uint64_t len = ce - base, from = cs - base;  // local positions from `from` on are the item's
-        uint64_t ob = 0;
-        if (PASS == 1) ob = w.rd_out[rd] + (w.w_cnt[g] - w.w_cnt[w.wfirst[rd]]) * mult;
-        uint64_t t_base = 0, e_base = 0, prev_valid = 0;
-        uint32_t prev_code = 0;
-        for (uint64_t p0 = 0; p0 < len; p0 += 64) {
-            const uint64_t p = p0 + lane;
-            const uint32_t code = p < len ? (uint32_t)base_code(a.seqs[base + p]) : 4u;
-            const uint64_t valid = __ballot(code < 4);
-            uint64_t kv = valid;
-            uint32_t kmer = code & 3;
-            for (uint32_t j = 1; j < k; ++j) {
-                kv &= (valid << j) | (prev_valid >> (64 - j));
-                const uint32_t up = __shfl_up(code, j), carry = __shfl(prev_code, (int)(64 + lane - j) & 63);
-                kmer |= ((lane >= j ? up : carry) & 3) << (2 * j);
-            }
-            const bool has = (kv >> lane) & 1;
-            const uint64_t t = t_base + __popcll(kv & lt);
-            if (has) keys[t & rmask] = lut[kmer];
-            __syncthreads();
-            const bool reports = has && t + 1 >= wsz;
-            uint32_t mn = 0xffffffffu;
-            if (reports) {
-                for (uint32_t j = 0; j < wsz; ++j) mn = min(mn, (uint32_t)keys[(t - j) & rmask]);
-                mins[t & rmask] = (uint8_t)mn;
-            }
-            __syncthreads();
-            const bool emit = reports && p >= from && (t + 1 == wsz || mins[(t - 1) & rmask] != mn);
-            const uint64_t em = __ballot(emit);
-            if (PASS == 1 && emit) {
-                const uint64_t e = e_base + __popcll(em & lt);
-                if (a.kind == SPX_DIGEST_PROMOTED) {
-                    a.out[ob + e] = (uint8_t)(mn > 2 ? mn : mn + 3);
-                } else {
-                    const uint32_t code_min = mn ^ a.xm;
-                    for (uint32_t j = 0; j < k; ++j)
-                        a.out[ob + e * k + j] = (uint8_t)letter_of((code_min >> (2 * (k - 1 - j))) & 3);
-                }
-            }
-            t_base += __popcll(kv);
-            e_base += __popcll(em);
-            prev_valid = valid;
-            prev_code = code;
-            __syncthreads();
-        }
-        if (PASS == 0 && lane == 0) w.w_cnt[g + 1] = e_base;
+        const uint64_t base = w.w_hs[g];  // (positions from cs on are the item's)
+        const uint64_t ob = PASS == 1 ? w.rd_out[rd] + (w.w_cnt[g] - w.w_cnt[w.wfirst[rd]]) * mult : 0;
+        const uint64_t e = wave_digest<PASS>(a, lds, base, ce - base, cs - base, ob);
+        if (PASS == 0 && threadIdx.x == 0) w.w_cnt[g + 1] = e;
     }
 }
 
@@ -1016,26 +934,24 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
     if (ix->force_digest_kernel == 1) lanes = a.wsz <= 8;
     if (ix->force_digest_kernel == 2) lanes = false;
     const uint64_t cus = (uint64_t)(ix->num_cus > 0 ? ix->num_cus : 256);
-    // (the scans' workspace: one buffer of its own, the last slot -- the scans of a call run one after the other on the stream)
-    auto scan_tmp = [&](void** out, size_t bytes) -> hipError_t {
+    // counts -> offsets, in place (the workspace: one buffer of its own, the last slot -- the scans of a call run one after
+    // the other on the stream)
+    auto scan = [&](uint64_t* v, uint64_t count, bool inclusive) -> int {
+        auto run = [&](void* tmp, size_t& bytes) {  // (hipCUB: the workspace's size with tmp == nullptr, else the scan)
+            return inclusive ? hipcub::DeviceScan::InclusiveSum(tmp, bytes, v, v, count, st)
+                             : hipcub::DeviceScan::ExclusiveSum(tmp, bytes, v, v, count, st);
+        };
+        size_t tmp_bytes = 0;
+        SPX_HIP(run(nullptr, tmp_bytes));
         spx_index::Scratch& sc = ix->digest_scr[spx_index::NDIGSCR - 1];
-        if (sc.cap < bytes) {
+        if (sc.cap < tmp_bytes) {
             if (sc.p) (void)hipFree(sc.p);
             sc.p = nullptr;
             sc.cap = 0;
-            const hipError_t e = hipMalloc(&sc.p, bytes + 4096);
-            if (e != hipSuccess) return e;
-            sc.cap = bytes + 4096;
+            SPX_HIP(hipMalloc(&sc.p, tmp_bytes + 4096));
+            sc.cap = tmp_bytes + 4096;
         }
-        *out = sc.p;
-        return hipSuccess;
-    };
-    auto scan_counts = [&]() -> int {  // counts -> offsets, in place
-        size_t tmp_bytes = 0;
-        SPX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_out_offs, d_out_offs, nreads + 1, st));
-        void* tmp = nullptr;
-        SPX_HIP(scan_tmp(&tmp, tmp_bytes));
-        SPX_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, d_out_offs, d_out_offs, nreads + 1, st));
+        SPX_HIP(run(sc.p, tmp_bytes));
         return SPX_OK;
     };
     // long reads of the default shape: a lane per chunk of 240 characters (k_digest_chunks)
@@ -1056,25 +972,12 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
         SPX_HIP(scr.get((void**)&c_count, (bound + 2) * 8));
         SPX_HIP(scr.get((void**)&c_rd, (bound + 2) * 4));
         SPX_HIP(scr.get((void**)&stash, total_chars + 64));
-        auto scan = [&](uint64_t* v, uint64_t count, bool inclusive) -> int {
-            size_t tmp_bytes = 0;
-            void* tmp = nullptr;
-            if (inclusive)
-                SPX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, v, v, count, st));
-            else
-                SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, v, v, count, st));
-            SPX_HIP(scan_tmp(&tmp, tmp_bytes));
-            if (inclusive)
-                SPX_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, v, v, count, st));
-            else
-                SPX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, v, v, count, st));
-            return SPX_OK;
-        };
         const unsigned gq = (unsigned)((nreads + 1 + 255) / 256), gc = (unsigned)((bound + 255) / 256);
-        k_dchunk_count<<<gq, 256, 0, st>>>(d_offs, nreads, first_chunk, bad);
+        k_split_count<DCHUNK><<<gq, 256, 0, st>>>(d_offs, nreads, first_chunk);
         int rc = scan(first_chunk, nreads + 1, false);
         if (rc != SPX_OK) return rc;
-        k_dchunk_fill<<<gq, 256, 0, st>>>(d_offs, nreads, first_chunk, bound, c_start, c_rd);
+        k_split_fill<DCHUNK><<<gq, 256, 0, st>>>(d_offs, nreads, first_chunk, bound, c_start, c_rd);
+        SPX_HIP(hipMemsetAsync(bad, 0, nreads * 4, st));
         SPX_HIP(hipMemsetAsync(c_count, 0, 8, st));
         a.out = stash;
         const uint64_t groups = (bound + 63) / 64;
@@ -1101,10 +1004,10 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
         SPX_HIP(scr.get((void**)&w_cnt, (wb + 2) * 8));
         WaveChunks wc{w_start, w_rd, w_hs, vk, wfirst, w_cnt, d_out_offs, wb};
         const unsigned gw = (unsigned)((wb + 255) / 256);
-        k_wchunk_count<<<gq, 256, 0, st>>>(d_offs, nreads, wfirst);
+        k_split_count<WCHUNK><<<gq, 256, 0, st>>>(d_offs, nreads, wfirst);
         rc = scan(wfirst, nreads + 1, false);
         if (rc != SPX_OK) return rc;
-        k_wchunk_fill<<<gq, 256, 0, st>>>(d_offs, nreads, wfirst, wb, w_start, w_rd);
+        k_split_fill<WCHUNK><<<gq, 256, 0, st>>>(d_offs, nreads, wfirst, wb, w_start, w_rd);
         const uint32_t gridw = (uint32_t)(wb < cus * 64 ? wb : cus * 64);
         k_wchunk_valid_ends<<<gridw, 64, 0, st>>>(aw, wc);
         k_wchunk_halo<<<gw, 256, 0, st>>>(aw, wc);
@@ -1160,7 +1063,7 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
             (a.wsz == 8 && k == 4) ? k_digest_lanes<SPX_DIGEST_DNA, true><<<grid, 64, lds_dyn, st>>>(a)
                        : k_digest_lanes<SPX_DIGEST_DNA, false><<<grid, 64, lds_dyn, st>>>(a);
         SPX_HIP(hipGetLastError());
-        int rc = scan_counts();
+        int rc = scan(d_out_offs, nreads + 1, true);
         if (rc != SPX_OK) return rc;
         if (park) {
             *parked = true;
@@ -1178,7 +1081,7 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
         const uint32_t grid = (uint32_t)(nreads < cus * 64 ? nreads : cus * 64);
         k_digest_wave<0><<<grid, 64, lds, st>>>(a);
         SPX_HIP(hipGetLastError());
-        int rc = scan_counts();
+        int rc = scan(d_out_offs, nreads + 1, true);
         if (rc != SPX_OK) return rc;
         k_digest_wave<1><<<grid, 64, lds, st>>>(a);
     }

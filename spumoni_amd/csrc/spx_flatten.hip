@@ -443,7 +443,7 @@ int build_fat(spx_index* ix) {
 // for_each_piece), so that a step is never more than span - 4 rows away from the row the compact encoding sends it to
 // (tools/ff_model.py; tests/piece_cuts_check.cpp holds the cut rule against its specification on the CPU).  The images
 // are known after a pass of their own over the run list (S, the heads' order, LF of every run start): it is made for an
-// index whose longest run has SPX_BALANCE_MIN_RUN (2048) positions or more -- an image covers no more runs than the run
+// index whose longest run has 2048 positions or more -- an image covers no more runs than the run
 // has positions -- and cuts where an image covers more than SPX_BALANCE_SPAN (8; 0: never) runs.  The new pieces are run
 // boundaries themselves and may push another image past the bound again, so the pass is repeated on its own output until
 // nothing is cut or SPX_BALANCE_PASSES (4) were made (the fourth cuts a few rows in 10^4: profiles/r03_balanced_pieces_passes.txt).
@@ -622,10 +622,9 @@ int flatten_on_device(spx_index* ix, const uint8_t* d_heads, const uint64_t* d_l
         SPX_HIP(hipStreamSynchronize(st));
     }
     uint32_t span = 8;
-    uint64_t min_run = 2048;
+    constexpr uint64_t min_run = 2048;
     int passes = 4;
     if (const char* e = getenv("SPX_BALANCE_SPAN")) span = (uint32_t)atoi(e);
-    if (const char* e = getenv("SPX_BALANCE_MIN_RUN")) min_run = (uint64_t)atoll(e);
     if (const char* e = getenv("SPX_BALANCE_PASSES")) passes = atoi(e) < 1 ? 1 : atoi(e);
     const bool want_balance = span > 0 && max_len >= min_run && max_len <= MASK40;
     RunList orig;

@@ -1096,10 +1096,8 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
     // the plain walk over compact rows has a body of its own (spx_walk_fast.inc); SPX_OLD_WALK=1 keeps the state
     // machine for it too (A/B runs, and the tests that hold the two against each other)
     static const bool old_walk = getenv("SPX_OLD_WALK") != nullptr;
-    // k_walk_fast also walks passes 1 and 2 of the chunked walk (SPX_PASS2_LANES=1: pass 2 on the state machine, for A/B runs)
-    static const bool pass2_lanes = getenv("SPX_PASS2_LANES") != nullptr;
-    constexpr int FCHUNK = CHUNK;
-    const bool fast = COMPACT && !(CHUNK == 2 && pass2_lanes) && args.only_flagged == nullptr && !old_walk && items < (1ull << 31);
+    // (k_walk_fast also walks passes 1 and 2 of the chunked walk)
+    const bool fast = COMPACT && args.only_flagged == nullptr && !old_walk && items < (1ull << 31);
     if (args.in_starts != nullptr && !(fast && CHUNK == 0)) {
         set_error("internal: parked reads (BatchArgs::in_starts) are taken by the plain k_walk_fast only");
         return SPX_E_ARG;
@@ -1137,7 +1135,6 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
     int want = target_waves / (WALK_TPB / 64);
     if (want < 1) want = 1;
     if (want < occ) occ = want;
-    unsigned tpb = WALK_TPB;
     uint64_t grid = (uint64_t)occ * ix->num_cus;
     const uint64_t need = (items + WALK_TPB - 1) / WALK_TPB;
     BatchArgs a = args;
@@ -1153,29 +1150,24 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
         grid = (waves + (WALK_TPB / 64) - 1) / (WALK_TPB / 64);
     } else if (need < grid) {
         // Fewer reads than lanes (long-read batches): the walk of a read is one dependent
-        // chain, so the batch is latency-bound.  Spread it: 64-thread blocks, one or more per
-        // SIMD, and only as many active lanes per wavefront as needed -- a wavefront whose few
-        // lanes sit in the same phase issues a fraction of the instructions per iteration.
-        tpb = 64;
-        small_batch = true;
+        // chain, so the batch is latency-bound.  Spread it: two wavefronts per SIMD, and only as
+        // many active lanes per wavefront as needed -- a wavefront whose few lanes sit in the same
+        // phase issues a fraction of the instructions per iteration.
         // (two per SIMD: 1.12 -> 1.10 ms for the 6 250-read share at r = 2e9, 0.87 -> 0.85 at r = 2^27; three and four are
         // slower again -- profiles/r04_c5_passes.txt)
-        static const int spread = getenv("SPX_SPREAD_WAVES") ? atoi(getenv("SPX_SPREAD_WAVES")) : 2;
-        const uint64_t waves = (uint64_t)ix->num_cus * 4 * (uint64_t)(spread > 0 ? spread : 1);  // wavefronts per SIMD to fill
+        small_batch = true;
+        const uint64_t waves = (uint64_t)ix->num_cus * 4 * 2;
         uint64_t lpw = (items + waves - 1) / waves;
         if (lpw < 1) lpw = 1;
         if (lpw > 64) lpw = 64;
         a.lanes_per_wave = (uint32_t)lpw;
-        grid = (items + lpw - 1) / lpw;
-        if (spread > 1) {  // (blocks of four wavefronts: a 64-thread block costs the LDS of a 256-thread one, 13 fit a CU)
-            tpb = WALK_TPB;
-            grid = (items + lpw * 4 - 1) / (lpw * 4);
-        }
+        // (blocks of four wavefronts: a 64-thread block costs the LDS of a 256-thread one, 13 fit a CU)
+        grid = (items + lpw * 4 - 1) / (lpw * 4);
     }
     // Reads are dealt by striding (rd += lanes): when the batch is a small multiple of the lanes, the last round leaves most of
     // them idle while a few finish (1.25 M reads on 262 144 lanes: 4.77 reads per lane, a fifth round for three lanes in four).
     // The grid is cut to the blocks that give every lane the same number of reads.
-    if (ix->force_lanes_per_wave == 0 && need >= grid && getenv("SPX_NO_EVEN_GRID") == nullptr) {
+    if (ix->force_lanes_per_wave == 0 && need >= grid) {
         const uint64_t lanes_all = grid * WALK_TPB;
         const uint64_t rounds = (items + lanes_all - 1) / lanes_all;
         const uint64_t even = (items + rounds * WALK_TPB - 1) / (rounds * WALK_TPB);
@@ -1186,16 +1178,14 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
     if (grid == 0) grid = 1;
     if (fast) {
         // (a launch that does not fill the chip, and pass 2 -- a few characters per chunk, then a long tail -- are latency
-        // chains: they take the body that issues its gather early; SPX_EARLY_GATHER=0 / 1 forces either, for A/B runs)
-        static const int early_env = getenv("SPX_EARLY_GATHER") ? atoi(getenv("SPX_EARLY_GATHER")) : -1;
-        const bool early = early_env >= 0 ? early_env != 0 : (FCHUNK == 2 || small_batch);
-        if (early)
-            k_walk_fast<MODE, DOC, NARROW, FCHUNK, true><<<(unsigned)grid, tpb, 0, stream>>>(ix->view, a);
+        // chains: they take the body that issues its gather early)
+        if (CHUNK == 2 || small_batch)
+            k_walk_fast<MODE, DOC, NARROW, CHUNK, true><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);
         else
-            k_walk_fast<MODE, DOC, NARROW, FCHUNK, false><<<(unsigned)grid, tpb, 0, stream>>>(ix->view, a);
+            k_walk_fast<MODE, DOC, NARROW, CHUNK, false><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);
         if (wrote_lengths) *wrote_lengths = MODE == SPX_MODE_PML;  // no bit mask, no expansion kernel
     } else
-        k_walk_lanes<MODE, DOC, COMPACT, NARROW, CHUNK><<<(unsigned)grid, tpb, 0, stream>>>(ix->view, a);
+        k_walk_lanes<MODE, DOC, COMPACT, NARROW, CHUNK><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);
     SPX_HIP(hipGetLastError());
     return SPX_OK;
 }
@@ -1275,98 +1265,12 @@ __global__ void k_chunk_scan(ChunkArgs ch, uint64_t nreads, uint32_t round, uint
     }
 }
 
-// Pass 3: per read, from its last chunk down, what is left of the wrong start values.
-template <int MODE, bool DOC, bool NARROW>
-__global__ void k_chunk_fix(const BatchArgs b) {
-    const uint64_t q = blockIdx.x * (uint64_t)WALK_TPB + threadIdx.x;
-    if (q >= b.nreads) return;
-    const uint64_t cs = b.ch.chunk_start[q], ce = b.ch.chunk_start[q + 1];
-    if (ce - cs < 2 || b.ch.read_fail[q]) return;
-    uint16_t* const len16 = reinterpret_cast<uint16_t*>(b.out_lengths);
-    uint16_t* const doc16 = reinterpret_cast<uint16_t*>(b.out_docs);
-    const uint8_t* const ch_flags = b.ch.flags - (b.offs[0] & ~7ull);  // as in the walk: relative to the batch
-    // corrections carried into the results of the walk that enters the next chunk down: its start
-    // values were the recorded end values of the chunk above, which are off by this much
-    bool c_on = false, cd_on = false;
-    uint32_t c_len = 0, c_doc = 0;
-    uint64_t c_smp = 0;
-    auto patch = [&](uint64_t from, uint64_t to, bool do_cnt, uint32_t dl, uint64_t ds, bool do_doc, uint32_t dv,
-                     bool& cnt_reset, bool& doc_reset) {
-        // indices from-1 down to `to`: counters get their offset until the first step that reset them,
-        // the document id its value until the first step that set it
-        cnt_reset = doc_reset = false;
-        uint64_t w8 = 0, have = ~0ull;  // flags eight at a time: the aligned group that holds index i
-        for (uint64_t i = from; i-- > to;) {
-            if ((i & ~7ull) != have) {
-                have = i & ~7ull;
-                w8 = *reinterpret_cast<const uint64_t*>(ch_flags + have);
-            }
-            const uint32_t f = (uint32_t)(w8 >> ((i & 7) * 8)) & 0xffu;
-            if (!cnt_reset) {
-                if (f & 1) {
-                    cnt_reset = true;
-                } else if (do_cnt) {
-                    if (MODE == SPX_MODE_PML) {
-                        if (NARROW)
-                            len16[i] = (uint16_t)(len16[i] + dl);
-                        else
-                            b.out_lengths[i] += dl;
-                    } else {
-                        b.out_pointers[i] += ds;
-                    }
-                }
-            }
-            if (DOC && !doc_reset) {
-                if (f & 2) {
-                    doc_reset = true;
-                } else if (do_doc) {
-                    if (NARROW)
-                        doc16[i] = (uint16_t)dv;
-                    else
-                        b.out_docs[i] = dv;
-                }
-            }
-            if (cnt_reset && (doc_reset || !DOC)) break;
-        }
-    };
-    for (uint64_t j = ce - 1; j-- > cs;) {
-        const ChunkDesc d = b.ch.desc[j];
-        const uint64_t B = d.gend, A = B - (d.len & CHUNK_LEN_MASK);
-        const SeamRec sr = b.ch.seams[j];
-        bool r_cnt, r_doc;
-        // pass-2 results [t, B): started from the recorded end values of chunk j + 1
-        if (c_on || cd_on) patch(B, sr.t, c_on, c_len, c_smp, cd_on, c_doc, r_cnt, r_doc);
-        const bool e_cnt = sr.reset_above & 1, e_doc = (sr.reset_above & 2) != 0;
-        const uint32_t L_true = sr.ext.length + ((c_on && !e_cnt) ? c_len : 0u);
-        const uint64_t S_true = sr.ext.sample + ((c_on && !e_cnt) ? c_smp : 0ull);
-        const uint32_t D_true = (cd_on && !e_doc) ? c_doc : sr.ext.doc;
-        if (!(sr.met & 1)) {
-            // the walk from above ran through the whole chunk: to the read's first character, or on into
-            // the chunk below (a later round of pass 2 entered it with this walk's state)
-            if (d.len & CHUNK_BOTTOM) break;
-            c_on = c_on && !e_cnt;
-            cd_on = cd_on && !e_doc;
-            continue;
-        }
-        // speculative results [A, t): counters differ from the true ones by a constant up to the first reset
-        const uint32_t dl = L_true - sr.spec_length;
-        const uint64_t ds = S_true - sr.spec_sample;
-        const bool fix_cnt = MODE == SPX_MODE_PML ? dl != 0 : ds != 0;
-        const bool fix_doc = DOC && D_true != sr.spec_doc;
-        patch(sr.t, A, fix_cnt, dl, ds, fix_doc, D_true, r_cnt, r_doc);
-        c_on = !r_cnt && fix_cnt;
-        c_len = dl;
-        c_smp = ds;
-        cd_on = DOC && !r_doc && fix_doc;
-        c_doc = D_true;
-    }
-}
-
-// Pass 3 by wavefronts: one wavefront per read, one lane per chunk (top down, 64 chunks at a time).  What a
-// chunk hands to the chunk below it (k_chunk_fix's c_on / c_len / ...) is a function of what it was handed and of
-// its own records; the hand-overs die at the first reset, so instead of following the chain chunk by chunk every
-// lane computes its hand-over from its upper neighbour's, again and again until nothing changes (a chain that is
-// k chunks long settles in k rounds; the usual one in two).  Then every lane patches its own chunk.
+// Pass 3: per read, from its last chunk down, what is left of the wrong start values.  One wavefront per read, one lane
+// per chunk (top down, 64 chunks at a time).  What a chunk hands to the chunk below it (a Carry: whether its counters and
+// document id are still off, and by how much) is a function of what it was handed and of its own records; the hand-overs
+// die at the first reset, so instead of following the chain chunk by chunk every lane computes its hand-over from its
+// upper neighbour's, again and again until nothing changes (a chain that is k chunks long settles in k rounds; the usual
+// one in two).  Then every lane patches its own chunk.
 template <int MODE, bool DOC, bool NARROW>
 __global__ void k_chunk_fix_wave(const BatchArgs b) {
     const uint64_t q = (blockIdx.x * (uint64_t)WALK_TPB + threadIdx.x) >> 6;
@@ -1639,22 +1543,14 @@ int run_chunked(spx_index* ix, BatchArgs a, uint64_t bound, hipStream_t stream) 
             a.ch, a.nreads, (uint32_t)round, a.ch.last_round, a.counters);
         SPX_HIP(hipGetLastError());
     }
-    static const bool fix_by_lanes = getenv("SPX_CHUNK_FIX_LANES") != nullptr;  // the round-3 kernel, for A/B
-    if (fix_by_lanes) {
-        const unsigned grid = (unsigned)((a.nreads + WALK_TPB - 1) / WALK_TPB);
-        k_chunk_fix<MODE, DOC, NARROW><<<grid, WALK_TPB, 0, stream>>>(a);
-    } else {
-        const unsigned grid = (unsigned)((a.nreads * 64 + WALK_TPB - 1) / WALK_TPB);
-        k_chunk_fix_wave<MODE, DOC, NARROW><<<grid, WALK_TPB, 0, stream>>>(a);
-    }
+    const unsigned wgrid = (unsigned)((a.nreads * 64 + WALK_TPB - 1) / WALK_TPB);  // (a wavefront per read)
+    k_chunk_fix_wave<MODE, DOC, NARROW><<<wgrid, WALK_TPB, 0, stream>>>(a);
     SPX_HIP(hipGetLastError());
     if (MODE == SPX_MODE_PML && a.out_class != nullptr) {
-        const unsigned cgrid = (unsigned)((a.nreads * 64 + WALK_TPB - 1) / WALK_TPB);
-        static const bool by_bins = getenv("SPX_CLASSIFY_BY_BINS") != nullptr;  // the round-2 kernel, for A/B
-        if (a.bin_width >= 8 && !by_bins)
-            k_classify_tiles<NARROW><<<cgrid, WALK_TPB, 0, stream>>>(a);
+        if (a.bin_width >= 8)
+            k_classify_tiles<NARROW><<<wgrid, WALK_TPB, 0, stream>>>(a);
         else
-            k_classify_reads<NARROW><<<cgrid, WALK_TPB, 0, stream>>>(a);
+            k_classify_reads<NARROW><<<wgrid, WALK_TPB, 0, stream>>>(a);
         SPX_HIP(hipGetLastError());
     }
     // reads in which a seam did not close: the plain walk (rare; results and class are overwritten)
@@ -1682,12 +1578,11 @@ int launch_walk_chunked(spx_index* ix, int mode, const BatchArgs& args, uint64_t
         SPX_HIP(hipGetDeviceProperties(&prop, ix->device));
         ix->num_cus = prop.multiProcessorCount;
     }
-    // what the walk keeps resident: launch_lanes' occupancy target for pass 1 (k_walk_fast; SPX_CHUNK_GEOM_WAVES overrides:
-    // the geometry below was laid out for 20 wavefronts per CU until round 4 lowered the plain walk's default to 16 / 12 --
-    // 623 000 chunks on 262 144 lanes were 2.4 rounds)
-    static const int geom_waves_env = getenv("SPX_CHUNK_GEOM_WAVES") ? atoi(getenv("SPX_CHUNK_GEOM_WAVES")) : 0;
+    // what the walk keeps resident: launch_lanes' occupancy target for pass 1 (k_walk_fast; the geometry below was laid out
+    // for 20 wavefronts per CU until round 4 lowered the plain walk's default to 16 / 12 -- 623 000 chunks on 262 144 lanes
+    // were 2.4 rounds)
     const bool side = mode == SPX_MODE_MS || args.out_docs != nullptr;
-    const int geom_waves = geom_waves_env > 0 ? geom_waves_env : (ix->waves_per_cu > 0 ? ix->waves_per_cu : (side ? 12 : 16));
+    const int geom_waves = ix->waves_per_cu > 0 ? ix->waves_per_cu : (side ? 12 : 16);
     const uint64_t lanes = (uint64_t)ix->num_cus * (uint64_t)geom_waves * 64;
     int mode_knob = ix->chunk_mode;                          // 0 automatic, 1 never, 2 always (tests)
     if (mode_knob == 1) return SPX_OK;

@@ -44,22 +44,6 @@ enum : uint32_t { A_STEP = 1, A_EMIT = 2, A_DECIDE = 4 };
 #define SPX_STEP_REPS 2
 #endif
 constexpr int STEP_REPS = SPX_STEP_REPS;
-// two consecutive MS pointers, 16 bytes of a line that the wavefront writes whole: non-temporal stores (the line is
-// complete and nobody reads it before the kernel ends; SPX_PTR_PLAIN: ordinary stores, for A/B runs)
-#ifndef SPX_PTR_PLAIN
-#define SPX_PTR_STORE2(p, a, b_)                                    \
-    do {                                                             \
-        __builtin_nontemporal_store((uint64_t)(a), (uint64_t*)(p));      \
-        __builtin_nontemporal_store((uint64_t)(b_), (uint64_t*)(p) + 1); \
-    } while (0)
-#else
-#define SPX_PTR_STORE2(p, a, b_) (*reinterpret_cast<P64x2*>(p) = P64x2{(a), (b_)})
-#endif
-#ifdef SPX_DOC_NT
-#define SPX_DOC_STORE2(p, v) __builtin_nontemporal_store((uint32_t)(v), reinterpret_cast<uint32_t*>(p))
-#else
-#define SPX_DOC_STORE2(p, v) (*reinterpret_cast<H16x2*>(p) = H16x2{(v)})
-#endif
 constexpr uint32_t OFF_LAST32 = 0xffffffffu;
 
 // the value of the lane beside this one (lanes 2j and 2j + 1 exchange): DPP quad_perm [1, 0, 3, 2]
@@ -87,8 +71,8 @@ __device__ __forceinline__ void lf_target_ct(uint32_t LFrun, uint32_t LFoff, uin
 // k_walk_lanes<..., 1> records; 2 = pass 2: a chunk is entered with the recorded end state of the chunk above it (Q_START)
 // and walked, its results written one value at a time over the speculative ones, until the walk stands where the
 // speculative walk stood at the same character -- asked at every checkpoint, whose record was fetched sixteen characters
-// ahead -- or the chunk ends; what k_walk_lanes<..., 2> does (SPX_PASS2_LANES=1 keeps that kernel for it), at one gather
-// per character instead of that kernel's two or three in a row.
+// ahead -- or the chunk ends; what k_walk_lanes<..., 2> does, at one gather per character instead of that kernel's two or
+// three in a row.
 // EARLY: the next iteration's gather is issued right after the repetitions, ahead of the iteration's output flushes -- for
 // launches that do not fill the chip (few long reads, the chunked walk's share, pass 2), where a wavefront's time is its
 // own latency chain (gather + ~400 dependent instructions an iteration): -6 % there, and +1 % on full launches, which
@@ -123,11 +107,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     // a PML-only index may keep, in the second half of a 32-byte fat slot, the ROW of the run the slot's jump lands in
     // (run sLFrun: the successor's landing and, when the predecessor lands in the same run, its landing too): the step
     // after such a jump goes on from that row without a landing gather (spx_flatten.hip, SPX_FAT_LROW)
-#ifdef SPX_EXP_FIXED_FLAGS  // experiment (headline configuration only): what the runtime-uniform flags cost as SGPR masks
-    constexpr bool lrow = false;
-#else
     const bool lrow = !AUX && fs == 32 && ix.aux == nullptr;
-#endif
     for (int t = threadIdx.x; t < 256; t += blockDim.x) {
         const LetterInfo li = ix.letters[t];
         s_hot[t] = HotLetter{li.bmul, li.qbeg != li.qend ? 1u : 0u, (uint64_t)(uintptr_t)(fat_b + li.fbase * fs)};
@@ -140,20 +120,12 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     const char* const off_b = reinterpret_cast<const char*>(b.offs);
     const uint32_t R = ix.r;
     const uint32_t fs_shift = fs == 32 ? 5 : 4;
-#ifdef SPX_EXP_FIXED_FLAGS
-    constexpr bool want_class = PML && CHUNK == 0;
-#else
     const bool want_class = PML && CHUNK == 0 && b.out_class != nullptr;
-#endif
     // PML lengths leave the walk as whole 64-character words, written by the WAVEFRONT: when a lane has collected the
     // reset bits of 64 characters (or its read ends) all 64 lanes write that stretch together -- one coalesced store
     // of 128 / 256 contiguous bytes instead of a lane's scattered stores (which is what made per-lane length stores
     // expensive: profiles/r02_store_experiments.txt) and instead of a second kernel over a bit mask
-#ifdef SPX_EXP_FIXED_FLAGS
-    constexpr bool want_len = PML && CHUNK != 2;
-#else
     const bool want_len = PML && CHUNK != 2 && b.out_lengths != nullptr;
-#endif
     const uint32_t lpw = b.lanes_per_wave;
     const uint32_t nlanes = (uint32_t)((((uint64_t)gridDim.x * blockDim.x) >> 6) * lpw);
     const uint32_t nitems = CHUNK ? (uint32_t)*b.ch.nchunks : (uint32_t)b.nreads;  // (the launcher keeps batches of 2^31 items and more on k_walk_lanes)
@@ -210,28 +182,12 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
 #endif
         // (by pairs only when enough lanes of the wavefront want 32 bytes: the exchange costs ~30 instructions an iteration,
         // and a wavefront of 16-byte gathers -- reads that do not match -- gets nothing for them)
-#ifdef SPX_EARLY_PAIR  // (A/B: the exchange also in the latency-bound form)
-        constexpr int pair_min = SPX_PAIR_MIN;
-#else
         // (EARLY launches are latency chains, not short of line lookups: the exchange would only lengthen the chain)
         constexpr int pair_min = EARLY ? 65 : SPX_PAIR_MIN;
-#endif
         if ((int)__popcll(__builtin_amdgcn_ballot_w64(ph != Q_DONE && (fl & F_WIDE))) < pair_min) {
             if (ph != Q_DONE) {
-#ifdef SPX_GATHER_NT  // experiment: the gathers as non-temporal loads (profiles/r04_gather_nt.txt)
-                {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
-                    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(addr));
-                    ga = V16{t.x, t.y, t.z, t.w};
-                    if (fl & F_WIDE) {
-                        const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(addr + 16));
-                        gb = V16{u.x, u.y, u.z, u.w};
-                    }
-                }
-#else
                 ga = *reinterpret_cast<const V16*>(addr);
                 if (fl & F_WIDE) gb = *reinterpret_cast<const V16*>(addr + 16);
-#endif
             }
         } else
         // A 32-byte gather as two loads of the same lane costs the memory pipeline two line lookups per lane; with the two
@@ -254,19 +210,11 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
             const bool do1 = odd ? w_for != 0 : live, do2 = odd ? live : w_for != 0;
             uint32_t r1x = 0, r1y = 0, r1z = 0, r1w = 0, r2x = 0, r2y = 0, r2z = 0, r2w = 0;
             if (do1) {
-#ifdef SPX_GATHER_NT
-                const u32x4 t = __builtin_nontemporal_load((GV16)(uintptr_t)a1);
-#else
                 const u32x4 t = *(GV16)(uintptr_t)a1;
-#endif
                 r1x = t.x, r1y = t.y, r1z = t.z, r1w = t.w;
             }
             if (do2) {
-#ifdef SPX_GATHER_NT
-                const u32x4 t = __builtin_nontemporal_load((GV16)(uintptr_t)a2);
-#else
                 const u32x4 t = *(GV16)(uintptr_t)a2;
-#endif
                 r2x = t.x, r2y = t.y, r2z = t.z, r2w = t.w;
             }
             // own first half; the second half is what the neighbour loaded for this lane (exchanged with every lane active: a
@@ -281,9 +229,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
         side_doc = 0;
         side_aux = Aux{0, 0};
         side_in = 0;
-#ifndef SPX_EXP_FIXED_FLAGS
         if (CHUNK == 0 && b.in_starts != nullptr && ph == Q_READ) side_in = b.in_starts[rd];
-#endif
         if (DOC && ph == Q_SAMP) side_doc = ix.rundocs[k];
         if (AUX && ph == Q_DIR) side_aux = ix.aux[length];
     };
@@ -378,11 +324,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                     base = u64of(ga.x, ga.y);
                     m = (uint32_t)(u64of(ga.z, ga.w) - base);
                 }
-#ifdef SPX_EXP_FIXED_FLAGS
-                ibase = base;
-#else
                 ibase = (CHUNK == 0 && b.in_starts != nullptr) ? side_in : base;
-#endif
                 if (m == 0) {
                     if (want_class) b.out_class[rd] = spx_class{0, 0, 0};
                     rd += nlanes;
@@ -730,10 +672,6 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                     // the lane's LDS group, which is complete at the line's lowest position (or the read's)
                     const uint32_t slot = ((uint32_t)base + xi) & (PGRP - 1);
                     const uint64_t pv = (sample & 0xffffffffffffull) | (DOC ? (uint64_t)doc << 48 : 0ull);
-#ifdef SPX_EXP_NOSTAGE  // experiment: the walk without its pointer / document staging and flush (results wrong)
-                    if (pv == 0x123456789abcull) s_ptrs[slot * PROW + tid] = pv;
-                    else
-#endif
                     if (pflush) {  // (the group above has not left yet: its slot PGRP - 1 is still needed)
                         phold = pv;
                         pheld = true;
@@ -841,12 +779,11 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                     const uint64_t v1 = s_ptrs[(e2 + 1) * PROW + (tid & ~63u) + from];
                     const bool ok0 = valid && p0 >= lo && p0 < hi, ok1 = valid && p0 + 1 >= lo && p0 + 1 < hi;
                     const uint64_t q0p = (uint64_t)((int64_t)(v0 << 16) >> 16), q1p = (uint64_t)((int64_t)(v1 << 16) >> 16);
-#ifdef SPX_EXP_NOPTR  // experiment: what do the pointer stores themselves cost (results wrong)
-                    if (ok0 && ok1 && q0p == 0x123456789abcull) {
-#else
                     if (ok0 && ok1) {
-#endif
-                        SPX_PTR_STORE2(b.out_pointers + p0, q0p, q1p);
+                        // 16 bytes of a line that the wavefront writes whole: non-temporal stores (the line is complete
+                        // and nobody reads it before the kernel ends)
+                        __builtin_nontemporal_store(q0p, b.out_pointers + p0);
+                        __builtin_nontemporal_store(q1p, b.out_pointers + p0 + 1);
                     } else if (ok0) {
                         b.out_pointers[p0] = q0p;
                     } else if (ok1) {
@@ -856,12 +793,8 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                         const uint32_t d0 = (uint32_t)(v0 >> 48), d1 = (uint32_t)(v1 >> 48);
                         if (NARROW) {
                             uint16_t* const dp = reinterpret_cast<uint16_t*>(b.out_docs) + p0;
-#ifdef SPX_EXP_NODOC
-                            if (ok0 && ok1 && d0 == 0xfffe)
-#else
                             if (ok0 && ok1)
-#endif
-                                SPX_DOC_STORE2(dp, d0 | (d1 << 16));
+                                *reinterpret_cast<H16x2*>(dp) = H16x2{d0 | (d1 << 16)};
                             else if (ok0)
                                 dp[0] = (uint16_t)d0;
                             else if (ok1)
@@ -961,17 +894,10 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 const uint64_t t = wbits >> lane;
                 const uint32_t v = t != 0 ? (uint32_t)__builtin_ctzll(t) : wnr - (wxi + lane);
                 if (lane < cnt) {
-#ifdef SPX_LEN_NT  // experiment: the wavefront's 128 / 256 bytes of lengths as non-temporal stores (profiles/r04_gather_nt.txt)
-                    if (NARROW)
-                        __builtin_nontemporal_store((uint16_t)v, reinterpret_cast<uint16_t*>(b.out_lengths) + (wbase + wxi + lane));
-                    else
-                        __builtin_nontemporal_store(v, b.out_lengths + (wbase + wxi + lane));
-#else
                     if (NARROW)
                         reinterpret_cast<uint16_t*>(b.out_lengths)[wbase + wxi + lane] = (uint16_t)v;
                     else
                         b.out_lengths[wbase + wxi + lane] = v;
-#endif
                 }
             }
         }

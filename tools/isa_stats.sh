@@ -1,6 +1,6 @@
 #!/bin/bash
 # Static figures of the walk kernels (no GPU needed): registers, LDS, spills, instruction lines per kernel.
-#   usage: bash tools/isa_stats.sh [extra hipcc flags, e.g. -DSPX_PTR_NT]      (assembly left in /tmp/isa/walk.s)
+#   usage: bash tools/isa_stats.sh [extra hipcc flags, e.g. -DSPX_PGRP=8]      (assembly left in /tmp/isa/walk.s)
 mkdir -p /tmp/isa
 [ -n "$ISA_REUSE" ] || /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -S --cuda-device-only "$@" \
   -o /tmp/isa/walk.s "$(dirname "$0")/../spumoni_amd/csrc/spx_walk.hip" 2>/dev/null
