@@ -101,7 +101,8 @@ void spx_index_free(spx_index *ix);
 /* get_bwt_stats() (compute_ms_pml.cpp:171-173, 739-741): n = bwt size, r = runs -- the runs of the
  * BWT as the files hold them.  (The flat layout may keep a run as several rows: one of 2^16 positions
  * or more, or one whose LF image covers many runs, is laid out as consecutive pieces of the same head;
- * spx_index_describe reports those rows as "flat_runs".  No result depends on it.)                    */
+ * spx_index_describe reports those rows as "flat_runs".  No result depends on it.)
+ * Limits, refused when the index is made: n <= 2^40 - 3 positions, r < 2^32 - 16 runs, document ids <= 65535. */
 int spx_index_stats(const spx_index *ix, uint64_t *n, uint64_t *r);
 /* bytes of HBM the flat layout occupies                                       */
 int spx_index_device_bytes(const spx_index *ix, uint64_t *bytes);

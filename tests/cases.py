@@ -50,3 +50,118 @@ def real_case(seed, n, letters, ndocs=3, device="cpu"):
     doc_lengths = np.diff([0] + cuts + [n]).tolist()
     raw = synth.index_from_text(torch.from_numpy(text).to(device), doc_lengths=doc_lengths)
     return raw, text
+
+
+# ---- indexes whose packed fields are full: n at the 40-bit limit, 16-bit document ids (test_gpu_field_widths.py) ----
+N_LIMIT = (1 << 40) - 3  # the largest BWT length the flatten step accepts (spx_flatten.hip: n > MASK40 - 2 is refused)
+WIDE_ALPHABETS = [list(b"ACGT"), list(b"ACGTN"), [3, 4, 5, 90, 127, 128, 129, 200, 255], [2, 60, 126, 127, 128, 254, 255],
+                  list(b"ACGTNRY"), [5, 6, 7, 8, 9, 10]]
+
+
+def wide_case(seed, n=N_LIMIT, r=3000, n_docs=65536, share=0.05):
+    """A statistical index of `r` runs and exactly `n` positions: neighbours distinct, one terminator run, most runs
+    1-5 long, `share` of them between 2^16 and 2^38 (the exponent is drawn, so every magnitude occurs; the largest are
+    halved until the others fit into n - 2^39), one topped up by at least 2^39 so that the lengths add up to n: that run has
+    a 40-bit length and holds half of all positions.  Thresholds, samples and document ids from synth.raw_from_runs; then
+    the corners a random draw does not hit are written over the neighbours of every seventh (samples) or fourth (document ids) long run: samples n-1, 0 (the MS `sample--`
+    wrap), single bits 24, 31, 32, 39 and their neighbours; document ids 0, 255, 256, 32768, 65535 (n_docs permitting).
+    Returns (raw, letters)."""
+    rng = np.random.default_rng(seed)
+    letters = WIDE_ALPHABETS[seed % len(WIDE_ALPHABETS)]
+    sigma = len(letters)
+    idx = np.cumsum(rng.integers(1, sigma, size=r)) % sigma  # steps of 1 .. sigma-1: neighbours differ
+    heads = np.asarray(letters, dtype=np.uint8)[idx].copy()
+    lens = rng.integers(1, 6, size=r).astype(np.int64)
+    big = np.flatnonzero(rng.random(r) < share)
+    big = big[big != r // 2]
+    assert big.size >= 8
+    e = rng.integers(16, 38, size=big.size)
+    lens[big] = (1 << e) + (rng.random(big.size) * (1 << e)).astype(np.int64)
+    heads[r // 2], lens[r // 2] = 0, 1
+    room = 1 << 39  # what the top-up adds at least: the longest run has 2^39 positions or more, a 40-bit length
+    assert n > (1 << 38)
+    while int(lens.sum()) > n - room:
+        j = big[np.argmax(lens[big])]
+        lens[j] //= 2
+    top = big[int(rng.integers(0, big.size))]
+    lens[top] += n - int(lens.sum())
+    assert int(lens.sum()) == n and lens.min() >= 1
+    raw = synth.raw_from_runs(torch.from_numpy(heads), torch.from_numpy(lens), seed, with_samples=True, n_docs=n_docs)
+    assert raw.n == n
+    sa_corners = [n - 1, 0, 1 << 24, 1 << 31, 1 << 32, 1 << 39, (1 << 32) - 1, (1 << 39) | (1 << 24) | 1, n - 2, (1 << 39) - 1]
+    doc_corners = [d for d in (0, 255, 256, 32768, 65535) if d < n_docs]
+    # a walk spends its time inside the long runs, so the runs its jumps land on are their neighbours: the corners go there
+    # (samples_start / start_runs_doc of the run after a long one, samples_last / end_runs_doc of the run before)
+    for arr, corners, step, shift in ((raw.ssa, sa_corners, 1, 0), (raw.esa, sa_corners, -1, 5), (raw.doc_start, doc_corners, 1, 1),
+                                      (raw.doc_end, doc_corners, -1, 3)):
+        at = big[::(7 if corners is sa_corners else 4)] + step
+        at = at[(at != r // 2) & (at > 0) & (at < r - 1)]  # (not the last run: every read starts there)
+        arr[torch.from_numpy(at)] = torch.tensor([corners[(i + shift) % len(corners)] for i in range(at.size)], dtype=torch.int64)
+    # every read starts on the last run's sample and document id, and a matching read keeps them: wide ones
+    if int(raw.esa[r - 1]) < (1 << 32):
+        raw.esa[r - 1] += 1 << 39
+    if n_docs > 256 and int(raw.doc_end[r - 1]) < 256:
+        raw.doc_end[r - 1] += 256
+    return raw, letters
+
+
+def wide_reads(raw, letters, seed, nreads=600, length=60):
+    """simulate_reads at positive fractions 0, 0.5 and 1 (`nreads` each), 3 % of the characters replaced by letters
+    the index does not have -- one below 128, one above."""
+    parts = [synth.simulate_reads(raw, nreads, length, seed=seed * 3 + i, positive_fraction=pf)[0].numpy()
+             for i, pf in enumerate((0.0, 0.5, 1.0))]
+    seqs = np.concatenate(parts).copy()
+    rng = np.random.default_rng(seed + 77)
+    absent = [[c for c in range(2, 128) if c not in letters][0], [c for c in range(255, 127, -1) if c not in letters][0]]
+    hit = rng.random(seqs.size) < 0.03
+    seqs[hit] = np.asarray(absent, dtype=np.uint8)[rng.integers(0, 2, size=int(hit.sum()))]
+    offs = np.arange(3 * nreads + 1, dtype=np.int64) * length
+    return seqs, offs
+
+
+def wide_reach(raw, want_ms, want_docs):
+    """What a test on a wide index must reach, asserted on its inputs and on the oracle's answers so that it cannot
+    pass vacuously; returns the measured shares."""
+    n = raw.n
+    ptr = want_ms["pointers"].astype(np.uint64)
+    wrapped = ptr >= (1 << 63)  # `sample--` below zero (the reference prints them as 20-digit numbers)
+    got = dict(longest_run=int(raw.lens.max()), ptr_ge_2_32=float((ptr >= (1 << 32)).mean()),
+               ptr_bits=int(ptr[~wrapped].max()).bit_length(), ptr_wrapped=int(wrapped.sum()),
+               doc_ge_256=float((want_docs >= 256).mean()), doc_max=int(want_docs.max()))
+    assert got["longest_run"] >= (1 << 39), got  # a length of 40 bits: offsets inside that run set bits 38 and 39
+    assert got["ptr_ge_2_32"] >= 0.90 and got["ptr_bits"] == 40 and int(ptr[~wrapped].max()) < n, got
+    assert got["doc_ge_256"] >= 0.90 and got["doc_max"] >= (1 << 15), got
+    for arr in (raw.doc_start, raw.doc_end):
+        assert set((0, 255, 256, 32768, 65535)) <= set(arr.tolist())
+    for arr in (raw.ssa, raw.esa):
+        vals = arr.numpy()
+        assert (vals == n - 1).any() and (vals == 0).any()
+        for bit in (24, 31, 32, 39):
+            assert (vals == (1 << bit)).any()
+    return got
+
+
+def walk_offsets(orc, raw, seqs, offs, nreads=40):
+    """The offsets inside their runs of the positions the reference's backward search visits on the first `nreads` reads
+    (compute_ms_pml.cpp:238-286, followed with the oracle's primitives): what the walk's `off`, LFoff + off and the
+    threshold comparison have to hold.  Vacuity measure only: no result is compared with it."""
+    n = orc.n
+    starts = (torch.cumsum(raw.lens, 0) - raw.lens).numpy()
+    out = []
+    for q in range(min(nreads, offs.size - 1)):
+        pos = n - 1
+        for c in seqs[offs[q]: offs[q + 1]][::-1].tolist():
+            nc = orc.rank(n, c)
+            if nc > 0 and not (pos < n and orc.at(pos) == c and c < 128):
+                rnk = orc.rank(pos, c)
+                thr, nxt = n + 1, pos
+                if rnk < nc:
+                    nxt = orc.select(rnk, c)
+                    thr = orc.threshold(orc.run_of_position(nxt))
+                if pos < thr and rnk > 0:
+                    nxt = orc.select(rnk - 1, c)
+                pos = nxt
+            pos = orc.LF(pos, c)
+            if pos < n:
+                out.append(pos - int(starts[np.searchsorted(starts, pos, side="right") - 1]))
+    return np.asarray(out, dtype=np.uint64)

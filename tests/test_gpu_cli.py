@@ -107,6 +107,44 @@ def test_cli_ms_report_doc(built, tmp_path):
     _run_both(tmp_path, ref, prefix, "reads.fa", seqs, offs, rng, ["-c", "-d", "-w", "60"], "-M")
 
 
+def _setup_many_docs(tmp_path, seed, ndocs, nreads=250):
+    """A real BWT over `ndocs` documents of a few characters each; <ref>.doc written by the package's own writer
+    (spumoni_amd/build_index.py: width ceil(log2(ndocs)), as src/doc_array.cpp:97-101 sizes it)."""
+    from spumoni_amd.build_index import write_doc_array
+    from tests.sdsl_files import write_null_db
+
+    letters = list(b"ACGT")
+    raw, text = cases.real_case(seed, max(6000, 3 * ndocs), letters, ndocs=ndocs)
+    ref = str(tmp_path / "ref")
+    open(ref + ".fa", "w").write(">dummy\n")
+    prefix = ref + ".fa"
+    raw.write_raw_files(prefix)
+    text.tofile(prefix + ".rawtext")
+    write_doc_array(prefix + ".doc", raw.doc_start.tolist(), raw.doc_end.tolist(), ndocs)
+    write_null_db(prefix + ".pmlnulldb", 4.0, [1, 2, 3, 4, 4, 4, 4, 4])
+    write_null_db(prefix + ".msnulldb", 9.0, [5, 9, 9, 9, 9, 9])
+    rng = np.random.default_rng(seed)
+    seqs, offs = cases.reads_mixed(rng, text, letters, nreads, 300, [ord("N")])
+    return raw, ref, prefix, seqs, offs, rng
+
+
+@pytest.mark.parametrize("ndocs,width", [(300, 9), (4097, 13), (65536, 16)])
+def test_cli_document_arrays_of_9_13_and_16_bits(built, tmp_path, ndocs, width):
+    """<ref>.doc is an sdsl int_vector of ceil(log2(#documents)) bits per entry: from 9 bits on the entries straddle
+    64-bit words, and at 16 bits the ids fill the device's field.  `run -d`, PML and MS: every output file is the
+    oracle harness's, .doc_numbers included -- and the ids in it really are that wide."""
+    raw, ref, prefix, seqs, offs, rng = _setup_many_docs(tmp_path, 60 + width, ndocs)
+    blob = open(prefix + ".doc", "rb").read()
+    assert blob[16] == width and int(np.frombuffer(blob[:8], dtype="<u8")[0]) == raw.r  # u64 entries, u64 bits, u8 width
+    top = ndocs // 2  # (the width is a function of the number of documents; the ids must reach its upper bits too)
+    assert int(raw.doc_start.max()) >= top and int(raw.doc_end.max()) >= top and int(raw.doc_end.max()) < ndocs
+    for mode in ("-P", "-M"):
+        _run_both(tmp_path, ref, prefix, "reads.fa", seqs, offs, rng, ["-d"], mode)
+        ids = np.array(" ".join(ln for ln in open(tmp_path / "orc" / "reads.fa.doc_numbers").read().splitlines()
+                                if not ln.startswith(">")).split(), dtype=np.int64)
+        assert ids.max() >= top and (ndocs < 4096 or (ids >= 256).mean() > 0.5), (mode, ids.max(), (ids >= 256).mean())
+
+
 def test_cli_fastq_content_in_fa_named_file(built, tmp_path):
     # validate() insists on a .fa name even for FASTQ content (include/spumoni_main.hpp:288-290)
     ref, prefix, seqs, offs, rng = _setup(tmp_path, 43, list(b"ACGT"), nreads=120)

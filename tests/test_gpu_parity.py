@@ -290,6 +290,55 @@ def test_limits_are_enforced(gpu):
         ix.query_host(capi.SPX_MODE_PML, rd, offs, want_docs=True)
 
 
+@pytest.mark.parametrize("wide_rows", [0, 1])
+def test_limits_exactly(gpu, oracle_mod, wide_rows, monkeypatch):
+    """The boundary pair of each limit.  n = 2^40 - 3 is the largest BWT length the flatten step takes (spx_flatten.hip:
+    n > MASK40 - 2 is refused): it builds and answers like the oracle -- a position in the last run, a sample n - 1 --
+    and n = 2^40 - 2, 2^40 - 1 and 2^40 are refused by name, after which the device still answers.  Document id 65 535
+    is accepted and comes back through both entry widths; 65 536 is refused.  With compact rows + pieces, and with the
+    general rows, whose len and LFoff then hold the 2^39 of the second run."""
+    if wide_rows:
+        monkeypatch.setenv("SPX_ROWS_WIDE", "1")
+    heads = torch.tensor([0, 65, 67, 65, 71], dtype=torch.uint8)
+    rd, offs = np.array([65, 67, 71, 65, 65, 71, 84, 67, 65], dtype=np.uint8), np.array([0, 4, 9])
+
+    def index_of(n, doc=65535):
+        lens = torch.tensor([1, 1 << 39, (1 << 38) + 5, 7, 0], dtype=torch.int64)
+        lens[4] = n - int(lens.sum())
+        raw = synth.raw_from_runs(heads, lens, 1, with_samples=True, n_docs=65536)
+        raw.esa[4], raw.ssa[1], raw.ssa[2], raw.esa[2] = n - 1, n - 1, 0, n - 2
+        raw.doc_start[1], raw.doc_end[4], raw.doc_end[2], raw.doc_start[2] = doc, 65535, 32768, 256
+        assert raw.n == n
+        return raw
+
+    small = capi.Index.from_raw(synth.RawIndex(heads=torch.tensor([0, 65, 67], dtype=torch.uint8), thr=torch.zeros(3, dtype=torch.int64),
+                                               lens=torch.tensor([1, 2, 3], dtype=torch.int64), n=6), 0)
+    n_max = (1 << 40) - 3
+    raw = index_of(n_max)
+    assert int(raw.lens[4]) > (1 << 37)  # the walk starts at n - 1: offset 2^37 and more inside the last run
+    ix = capi.Index.from_raw(raw, 0)
+    assert ix.n == n_max and ix.describe()["compact_rows"] == 1 - wide_rows
+    orc = oracle_mod.OracleIndex.from_raw(raw)
+    w = orc.ms(rd, offs, want_docs=True)
+    assert int(w["docs"].max()) == 65535 and int(w["pointers"].astype(np.uint64).max()) >= (1 << 39)
+    for bits in (16, 32):
+        got = ix.query_host(capi.SPX_MODE_MS, rd, offs, want_lengths=False, want_docs=True, bits=bits)
+        assert np.array_equal(got["pointers"], w["pointers"]) and np.array_equal(got["docs"], w["docs"])
+        wl, wd = orc.pml(rd, offs, want_docs=True)
+        got = ix.query_host(capi.SPX_MODE_PML, rd, offs, want_docs=True, bits=bits)
+        assert np.array_equal(got["lengths"], wl) and np.array_equal(got["docs"], wd) and int(wd.max()) == 65535
+    _compare_all(oracle_mod, raw, None, rd, offs, ix=ix)
+    for n in (n_max + 1, n_max + 2, n_max + 3):
+        with pytest.raises(capi.SpxError, match="exceeds the 40-bit position field"):
+            capi.Index.from_raw(index_of(n), 0)
+        assert small.query_host(capi.SPX_MODE_PML, rd, offs)["lengths"].size == rd.size  # the device still answers
+    with pytest.raises(capi.SpxError, match="65535"):
+        capi.Index.from_raw(index_of(1000 + (1 << 39) + (1 << 38), doc=65536), 0)
+    assert np.array_equal(ix.query_host(capi.SPX_MODE_PML, rd, offs)["lengths"], orc.pml(rd, offs))
+    ix.close()
+    small.close()
+
+
 @pytest.mark.parametrize("bshift,wide_rows,all_esc", [(0, 0, 0), (2, 1, 0), (5, 0, 0), (9, 1, 0), (0, 0, 1), (3, 1, 1),
                                                       ("0.05:1.0", 0, 0), ("0.8:0.7", 1, 0), ("3:0.5", 0, 1),
                                                       ("12:0.0", 0, 0)])

@@ -45,7 +45,8 @@ def test_text_streams_are_the_reference_bytes(oracle_mod, seed, letters):
     assert _fill(got["text"][2], got["line_start"][2], ids) == _expect(docs, offs, ids)
     f, a, b, s = oracle_mod.classify(lens, offs, 20, 6)
     assert np.array_equal(got["class"]["above"], a) and np.array_equal(got["class"]["below"], b)
-    # MS: lengths, pointers (up to 13 digits), document ids
+    # MS: lengths, pointers, document ids (4 digits and 1 digit here; the 13-digit pointers and 5-digit ids the 64-bit path
+    # is for are in tests/test_gpu_field_widths.py::test_text_on_the_device_at_full_width)
     ix.set_text(__import__("torch").from_numpy(text.copy()))
     w = orc.ms(seqs, offs, want_docs=True, text=text)
     got = ix.query_text(capi.SPX_MODE_MS, seqs, offs, gap, capi.SPX_TEXT_LENGTHS | capi.SPX_TEXT_POINTERS | capi.SPX_TEXT_DOCS)

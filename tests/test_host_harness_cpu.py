@@ -61,6 +61,13 @@ def test_cli_fastq_validation_and_serialised_index(on_fake_device, tmp_path):
     T.test_cli_reads_the_serialised_index(None, tmp_path / "ser")
 
 
+@pytest.mark.parametrize("ndocs,width", [(300, 9), (4097, 13), (65536, 16)])
+def test_cli_document_arrays_whose_entries_straddle_words(on_fake_device, tmp_path, ndocs, width):
+    """host/index_files.cpp::read_int_vector on <ref>.doc files of 9, 13 and 16 bits per entry (every file the other CLI
+    tests read has at most 3): `run -d`, PML and MS, the same bytes as the oracle harness."""
+    _cli().test_cli_document_arrays_of_9_13_and_16_bits(None, tmp_path, ndocs, width)
+
+
 def test_cli_fatal_errors_come_in_read_order(on_fake_device, tmp_path, oracle_mod):
     T = _cli()
     (tmp_path / "a").mkdir()

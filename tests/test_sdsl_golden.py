@@ -46,6 +46,56 @@ def test_int_vector_width_40_crosses_a_word(built_all, tmp_path):
     assert dump(tmp_path, "int_vector", blob) == (0, f"{0x123456789A} {0xFFFFFFFFFF}", "")
 
 
+# 9 bits per entry (a document array of 257 .. 512 documents, src/doc_array.cpp:97-101): eight values, 72 bits, two
+# words; value i sits at bit 9 i, and the eighth (bit 63) straddles the words.
+#   1 << 0 = 0x1; 256 << 9 = 0x20000; 511 << 18 = 0x7FC0000; 0 << 27; 300 << 36 = 0x12C0_0000_0000;
+#   5 << 45 = 0xA000_0000_0000; 128 << 54 = 0x2000_0000_0000_0000; 257 = 0b1_0000_0001 at bit 63: its lowest bit is
+#   bit 63 of word 0 (0x8000_0000_0000_0000), the other eight (257 >> 1 = 128) are the low bits of word 1.
+#   word 0 = 0xA000_B2C0_07FE_0001 (little-endian 01 00 FE 07 C0 B2 00 A0), word 1 = 0x80
+INT_VECTOR_9 = ([1, 256, 511, 0, 300, 5, 128, 257], bytes.fromhex("4800000000000000" "09" "0100FE07C0B200A0" "8000000000000000"))
+# 16 bits per entry (32 769 .. 65 536 documents): five values, 80 bits, two words; four values fill word 0 exactly:
+#   0 | 255 << 16 | 256 << 32 | 32768 << 48 = 0x8000_0100_00FF_0000 (little-endian 00 00 FF 00 00 01 00 80), word 1 = 0xFFFF
+INT_VECTOR_16 = ([0, 255, 256, 32768, 65535], bytes.fromhex("5000000000000000" "10" "0000FF0000010080" "FFFF000000000000"))
+
+
+@pytest.mark.parametrize("vals,blob", [INT_VECTOR_9, INT_VECTOR_16], ids=["9_bits", "16_bits"])
+def test_int_vector_widths_of_a_document_array(built_all, tmp_path, vals, blob):
+    """The host reader on the hand-derived bytes, and the package's writers (spumoni_amd/sdsl_streams.py,
+    spumoni_amd/build_index.py; the package has no reader of its own) and the tests' writer giving exactly those bytes."""
+    assert dump(tmp_path, "int_vector", blob) == (0, " ".join(str(v) for v in vals), "")
+    from spumoni_amd import build_index, sdsl_streams
+    from tests import sdsl_files
+
+    width = blob[8]
+    assert sdsl_streams._int_vector(vals, width) == blob
+    assert build_index._int_vector(vals, width) == blob
+    assert sdsl_files._int_vector(vals, width) == blob
+
+
+@pytest.mark.parametrize("width", range(1, 17))
+def test_doc_array_round_trip_every_width(built_all, tmp_path, width):
+    """<ref>.doc as the package writes it for 2^width documents, read back by the host reader: 203 entries (not a
+    multiple of 64, so the last word is partial), the largest id, zero and alternating bit patterns among them."""
+    import numpy as np
+
+    from spumoni_amd.build_index import write_doc_array
+
+    rng = np.random.default_rng(width)
+    top = (1 << width) - 1
+    ds = rng.integers(0, top + 1, size=203).tolist()
+    de = rng.integers(0, top + 1, size=203).tolist()
+    ds[:4] = [top, 0, 0x5555 & top, 0xAAAA & top]
+    de[-3:] = [0, top, top >> 1]
+    path = tmp_path / "x.doc"
+    write_doc_array(str(path), ds, de, 1 << width)
+    blob = path.read_bytes()
+    size = 9 + 8 * ((203 * width + 63) // 64)  # u64 bits, u8 width, the words
+    assert len(blob) == 8 + 2 * size and struct.unpack("<Q", blob[:8])[0] == 203
+    assert blob[16] == max(width, 1) and struct.unpack("<Q", blob[8:16])[0] == 203 * width
+    assert dump(tmp_path, "int_vector", blob[8: 8 + size]) == (0, " ".join(map(str, ds)), "")
+    assert dump(tmp_path, "int_vector", blob[8 + size:]) == (0, " ".join(map(str, de)), "")
+
+
 def test_int_vector_truncated_is_an_error(built_all, tmp_path):
     blob = bytes.fromhex("5000000000000000" "28" "9A78563412FFFFFF")  # second word missing
     rc, _, err = dump(tmp_path, "int_vector", blob)
