@@ -819,6 +819,7 @@ static int query_device_impl(spx_index* ix, int mode, const uint8_t* d_seqs, con
     // the previous one (queries on one index are serialised, as the header promises)
     if (ix->have_timing && ix->last_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_done, 0));
     SPX_HIP(hipMemsetAsync(ix->counters, 0, sizeof(WalkCounters), st));
+    ix->claim_used = false;
     BatchArgs a{};
     a.seqs = d_seqs;
     a.offs = d_offsets;
@@ -976,6 +977,7 @@ static int run_pipelined(spx_index* ix, int mode, const uint8_t* seqs, const uin
     }
     if (ix->have_timing && ix->last_stream != s_k) SPX_HIP(hipStreamWaitEvent(s_k, ix->ev_done, 0));
     SPX_HIP(hipMemsetAsync(ix->counters, 0, sizeof(WalkCounters), s_k));
+    ix->claim_used = false;
     SPX_HIP(hipEventRecord(ix->ev0, s_k));
     // SPX_PIPE_TRACE=1: when every piece's copy-in, walk and copy-out ended, on stderr (timed events of their own)
     static const bool trace = getenv("SPX_PIPE_TRACE") != nullptr;

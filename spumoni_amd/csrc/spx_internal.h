@@ -33,6 +33,10 @@ struct WalkCounters {
     unsigned long long dir_loads;
     unsigned long long error;      // non-zero: a structural invariant was violated
     unsigned long long pad_;
+    // the next read index (less the launch's lanes) that the plain k_walk_fast launch of a batch with more reads than lanes
+    // hands out (spx_walk_fast.inc: the dynamic deal).  Zero when that launch starts: zeroed with the rest once per call,
+    // and by launch_lanes itself before a call's second such launch (spx_index::claim_used)
+    unsigned long long claim;
 };
 
 // ---- long reads: exact speculative chunking (spx_walk.hip) -----------------------
@@ -127,6 +131,9 @@ struct BatchArgs {
     // [((offs[q] - offs[0]) >> 7) + q, ...) (pairs of different reads never overlap), bit p & 63 of word p >> 6
     // for character p of the read.
     uint64_t* len_mask;
+    // k_walk_fast, plain and full launches: the word the wavefronts claim their reads from after the first, strided round
+    // (&counters->claim; null: every round is strided).  Set by launch_lanes.
+    unsigned long long* claim;
     uint64_t len_mask_pairs;  // 16-byte pairs len_mask holds (sized from total_chars: checked, the caller may be wrong)
 };
 
@@ -176,6 +183,7 @@ struct spx_index {
     bool dig_used = false;
     spx::DevIndex view{};
     spx::WalkCounters* counters = nullptr;
+    bool claim_used = false;  // a launch of this call has claimed reads from counters->claim since the counters were zeroed
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
     bool have_timing = false;
     hipStream_t last_stream = nullptr;

@@ -1164,10 +1164,22 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
         // (blocks of four wavefronts: a 64-thread block costs the LDS of a 256-thread one, 13 fit a CU)
         grid = (items + lpw * 4 - 1) / (lpw * 4);
     }
-    // Reads are dealt by striding (rd += lanes): when the batch is a small multiple of the lanes, the last round leaves most of
-    // them idle while a few finish (1.25 M reads on 262 144 lanes: 4.77 reads per lane, a fifth round for three lanes in four).
-    // The grid is cut to the blocks that give every lane the same number of reads.
-    if (ix->force_lanes_per_wave == 0 && need >= grid) {
+    // How the reads are dealt.  The plain walk of a batch with more reads than resident lanes deals them on demand: the
+    // first round by lane index, the rest claimed by the wavefronts from counters->claim as their lanes end reads
+    // (spx_walk_fast.inc), on the full resident grid -- reads cost unequally, and a fixed deal runs as long as its unluckiest
+    // lane (the headline's shuffled half-positive batch: 10 % over the sum of its parts, profiles/mix_penalty_before.txt).
+    // The claim word must be zero when the launch starts: the call's memset of the counters did that for the call's first
+    // such launch, a later one (the pieces of a pipelined host batch) zeroes it again, in stream order.
+    const bool dynamic = fast && CHUNK == 0 && ix->force_lanes_per_wave == 0 && !small_batch && items > grid * WALK_TPB;
+    if (dynamic) {
+        a.claim = &ix->counters->claim;
+        if (ix->claim_used) SPX_HIP(hipMemsetAsync(a.claim, 0, sizeof(unsigned long long), stream));
+        ix->claim_used = true;
+    }
+    // Everything else is dealt by striding (item += lanes): when the batch is a small multiple of the lanes, the last round
+    // leaves most of them idle while a few finish (1.25 M chunks on 262 144 lanes: 4.77 per lane, a fifth round for three
+    // lanes in four).  The grid is cut to the blocks that give every lane the same number of items.
+    if (!dynamic && ix->force_lanes_per_wave == 0 && need >= grid) {
         const uint64_t lanes_all = grid * WALK_TPB;
         const uint64_t rounds = (items + lanes_all - 1) / lanes_all;
         const uint64_t even = (items + rounds * WALK_TPB - 1) / (rounds * WALK_TPB);
@@ -1179,7 +1191,9 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
     if (fast) {
         // (a launch that does not fill the chip, and pass 2 -- a few characters per chunk, then a long tail -- are latency
         // chains: they take the body that issues its gather early)
-        if (CHUNK == 2 || small_batch)
+        if (dynamic)
+            k_walk_fast<MODE, DOC, NARROW, 0, false, true><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);
+        else if (CHUNK == 2 || small_batch)
             k_walk_fast<MODE, DOC, NARROW, CHUNK, true><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);
         else
             k_walk_fast<MODE, DOC, NARROW, CHUNK, false><<<(unsigned)grid, WALK_TPB, 0, stream>>>(ix->view, a);

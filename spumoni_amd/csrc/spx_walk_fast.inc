@@ -29,7 +29,7 @@
 // Q_FATJ, Q_QS, Q_DIR, Q_SAMP (samples_start / start_runs_doc of the run a byte >= 128 stays on) -- which share
 // one switch.
 
-enum : uint32_t { Q_LAND = 0, Q_FAT = 1, Q_STEP = 2, Q_READ = 3, Q_CHARS = 4, Q_FATJ = 5, Q_QS = 6, Q_DIR = 7, Q_DONE = 8, Q_SAMP = 9, Q_START = 10 };
+enum : uint32_t { Q_LAND = 0, Q_FAT = 1, Q_STEP = 2, Q_READ = 3, Q_CHARS = 4, Q_FATJ = 5, Q_QS = 6, Q_DIR = 7, Q_DONE = 8, Q_SAMP = 9, Q_START = 10, Q_WANT = 11 };
 enum : uint32_t {
     F_EMB = 1,     // this iteration's gather brought the row of run LFrun along (the lane landed on a row from memory)
     F_NOROW = 2,   // the lane stands on (k, off) knowing only the head of run k (low byte of q1)
@@ -45,6 +45,13 @@ enum : uint32_t { A_STEP = 1, A_EMIT = 2, A_DECIDE = 4 };
 #endif
 constexpr int STEP_REPS = SPX_STEP_REPS;
 constexpr uint32_t OFF_LAST32 = 0xffffffffu;
+// reads a wavefront takes from the batch's claim word at a time (BatchArgs::claim): 64 / 128 / 256 measured alike on the
+// headline batch (profiles/dynamic_deal_ab.txt); the smallest leaves the least ragged end
+#ifndef SPX_CHUNK_CLAIM
+#define SPX_CHUNK_CLAIM 64
+#endif
+constexpr uint32_t CHUNK_CLAIM = SPX_CHUNK_CLAIM;
+static_assert(CHUNK_CLAIM >= 64, "a claim covers at least one iteration's worst case: 64 lanes ending a read each");
 
 // the value of the lane beside this one (lanes 2j and 2j + 1 exchange): DPP quad_perm [1, 0, 3, 2]
 __device__ __forceinline__ uint32_t dpp_swap1(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true); }
@@ -77,7 +84,16 @@ __device__ __forceinline__ void lf_target_ct(uint32_t LFrun, uint32_t LFoff, uin
 // launches that do not fill the chip (few long reads, the chunked walk's share, pass 2), where a wavefront's time is its
 // own latency chain (gather + ~400 dependent instructions an iteration): -6 % there, and +1 % on full launches, which
 // therefore keep the gather at the top of the iteration (profiles/r04_early_gather.txt).
-template <int MODE, bool DOC, bool NARROW, int CHUNK = 0, bool EARLY = false>
+// How the items are dealt.  By striding (a lane's next item is nlanes after its last) everywhere but in the plain walk of a
+// batch with more reads than lanes (DYN; BatchArgs::claim is the word: CHUNK == 0, not EARLY).  There only the first round is strided;
+// after it a lane that ends a read (Q_WANT) is handed the next index of its WAVEFRONT's reservoir -- up to two ranges of
+// read indices in scalar registers, handed out by ballot + mbcnt once per iteration, after the repetitions -- and the
+// wavefront refills the reservoir ahead of need with one atomicAdd(claim, CHUNK_CLAIM) by one lane, issued together with
+// an iteration's gather and looked at after that gather has returned (like side_in / side_doc / side_aux), so nobody ever
+// waits for the atomic alone.  Reads cost unequally (one that matches takes ~35 iterations, a random one ~48): under
+// striding a lane's total is a draw, a wavefront runs as long as its slowest lane and the launch as long as its slowest
+// wavefront (DESIGN.md 4.1, profiles/mix_penalty_before.txt).  Which lane walks which read is not observable.
+template <int MODE, bool DOC, bool NARROW, int CHUNK = 0, bool EARLY = false, bool DYN = false>
 __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const BatchArgs b) {
     constexpr bool AUX = (MODE == SPX_MODE_MS) || DOC;  // per-jump side data (samples / doc ids)
     constexpr bool PML = MODE == SPX_MODE_PML;
@@ -136,6 +152,14 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     const char* const item_b = CHUNK ? reinterpret_cast<const char*>(b.ch.desc) : off_b;
     constexpr uint32_t ITEM_BYTES = CHUNK ? sizeof(ChunkDesc) : 8;
     const uint32_t tid = threadIdx.x;
+    static_assert(!DYN || (CHUNK == 0 && !EARLY), "only the plain, full launch deals its reads on demand");
+    uint32_t w_n0 = 0, w_e0 = 0, w_n1 = 0, w_e1 = 0;  // the reservoir: [w_n0, w_e0), then [w_n1, w_e1)
+    bool w_pend = false;  // a claim goes out with the next gather / is in flight with this one
+    bool w_dry = false;   // the batch has no reads beyond what the wavefront's last claim returned
+    // (the first claims are spread over the first 32 iterations -- nobody needs a read before its first one ends -- or
+    // every wavefront of the launch would be at the claim word in the same microsecond)
+    uint32_t w_wait = DYN ? (uint32_t)((((uint64_t)blockIdx.x * blockDim.x + tid) >> 6) & 31u) + 1u : 0u;
+    unsigned long long claimed = 0;
 
     uint32_t rd = (uint32_t)((((uint64_t)blockIdx.x * blockDim.x + tid) >> 6) * lpw) + (tid & 63);
     uint32_t ph = (rd < nitems && (tid & 63) < lpw) ? Q_READ : Q_DONE;
@@ -229,9 +253,11 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
         side_doc = 0;
         side_aux = Aux{0, 0};
         side_in = 0;
+        claimed = 0;
         if (CHUNK == 0 && b.in_starts != nullptr && ph == Q_READ) side_in = b.in_starts[rd];
         if (DOC && ph == Q_SAMP) side_doc = ix.rundocs[k];
         if (AUX && ph == Q_DIR) side_aux = ix.aux[length];
+        if (DYN && w_pend && (tid & 63) == 0) claimed = atomicAdd(b.claim, (unsigned long long)CHUNK_CLAIM);
     };
     if (EARLY) issue_gather();
     while (__builtin_amdgcn_ballot_w64(ph != Q_DONE) != 0) {
@@ -310,7 +336,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
             }
         } else if (ph == Q_STEP) {
             act = A_STEP;  // the repetitions ran out while the lane was standing
-        } else if (ph != Q_DONE && ph != Q_SAMP) {
+        } else if (ph != Q_DONE && ph != Q_SAMP && (!DYN || ph != Q_WANT)) {
             // ---- the rare phases ----
             if (ph == Q_READ) {
                 if (CHUNK) {  // ChunkDesc: gend, len | flags << 29, read
@@ -327,9 +353,9 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 ibase = (CHUNK == 0 && b.in_starts != nullptr) ? side_in : base;
                 if (m == 0) {
                     if (want_class) b.out_class[rd] = spx_class{0, 0, 0};
-                    rd += nlanes;
-                    ph = rd < nitems ? Q_READ : Q_DONE;
-                    addr = item_b + (uint64_t)rd * ITEM_BYTES;
+                    rd += DYN ? 0u : nlanes;
+                    ph = DYN ? Q_WANT : (rd < nitems ? Q_READ : Q_DONE);
+                    addr = DYN ? rows_b : item_b + (uint64_t)rd * ITEM_BYTES;
                 } else {
                     if (NARROW && CHUNK == 0 && m >= 65536) atomicAdd(&b.counters->error, 1ull);  // 16-bit outputs cannot hold this read's values
                     x = m;
@@ -723,9 +749,9 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                         const bool ab = bin_max >= b.max_value_thr;
                         b.out_class[rd] = spx_class{sum_max + bin_max, above + (ab ? 1u : 0u), below + (ab ? 0u : 1u)};
                     }
-                    rd += nlanes;
-                    ph = rd < nitems ? Q_READ : Q_DONE;
-                    addr = item_b + (uint64_t)rd * ITEM_BYTES;
+                    rd += DYN ? 0u : nlanes;
+                    ph = DYN ? Q_WANT : (rd < nitems ? Q_READ : Q_DONE);
+                    addr = DYN ? rows_b : item_b + (uint64_t)rd * ITEM_BYTES;
                     fl = 0;
                     act = 0;
                 } else {
@@ -748,6 +774,49 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
             ph = Q_STEP;  // still standing: go on in the next iteration (the gather is a dummy)
             addr = rows_b;
             fl &= ~(F_WIDE | F_EMB);
+        }
+        if (DYN) {
+            // ---- the dynamic deal (all of it on wave-uniform values) ----
+            if (w_pend) {  // the claim that went out with this iteration's gather: reads [nlanes + claimed, ... + CHUNK_CLAIM)
+                const uint64_t c0 = (uint64_t)nlanes + u64of((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)claimed),
+                                                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(claimed >> 32)));
+                const uint64_t c1 = c0 + CHUNK_CLAIM;
+                w_n1 = (uint32_t)(c0 < nitems ? c0 : nitems);  // (a claim past the end is clipped)
+                w_e1 = (uint32_t)(c1 < nitems ? c1 : nitems);
+                w_dry = c1 >= nitems;  // (the word only grows: a later claim would lie past the end)
+                w_pend = false;
+            }
+            if (w_n0 == w_e0) {  // the first range is used up: the second takes its place
+                w_n0 = w_n1;
+                w_e0 = w_e1;
+                w_n1 = w_e1 = 0;
+            }
+            const uint64_t wants = __builtin_amdgcn_ballot_w64(ph == Q_WANT);
+            if (wants != 0) {
+                // the j-th lane that wants a read takes the reservoir's j-th index; a lane that finds it empty parks for an
+                // iteration (a dummy gather, like Q_STEP's) while a claim is on its way, and is done when none can come
+                const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(wants >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wants, 0u));
+                const uint32_t have0 = w_e0 - w_n0, have1 = w_e1 - w_n1, nw = (uint32_t)__popcll(wants);
+                const bool over = !w_pend && w_dry;
+                if (ph == Q_WANT) {
+                    const bool got = j < have0 + have1;
+                    rd = j < have0 ? w_n0 + j : w_n1 + (j - have0);
+                    ph = got ? Q_READ : (over ? Q_DONE : Q_WANT);
+                    addr = got ? item_b + (uint64_t)rd * ITEM_BYTES : rows_b;
+                }
+                const uint32_t t0 = nw < have0 ? nw : have0, t1 = (nw - t0) < have1 ? (nw - t0) : have1;
+                w_n0 += t0;
+                w_n1 += t1;
+                if (nw > have0 + have1) w_wait = 0;  // (lanes are parked: no reason left to hold the claim back)
+                if (w_n0 == w_e0) {
+                    w_n0 = w_n1;
+                    w_e0 = w_e1;
+                    w_n1 = w_e1 = 0;
+                }
+            }
+            // refill ahead of need: the next iteration can take at most 64 reads (a lane ends one read per iteration)
+            w_wait -= w_wait != 0 ? 1u : 0u;
+            w_pend = !w_dry && w_wait == 0 && w_n1 == w_e1 && (w_e0 - w_n0) < 64u;
         }
         if (EARLY) issue_gather();  // the next iteration's
         if (MODE == SPX_MODE_MS && CHUNK != 2) {
@@ -928,6 +997,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     (void)cka;
     (void)ckb;
     (void)w_again;
+    (void)w_n0, (void)w_e0, (void)w_n1, (void)w_e1, (void)w_pend, (void)w_dry, (void)w_wait, (void)claimed;
     // every character of the batch is one step
     if (CHUNK != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&b.counters->steps, (unsigned long long)(b.offs[b.nreads] - b.offs[0]));
 }
