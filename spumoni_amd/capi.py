@@ -449,6 +449,51 @@ class Index:
             out["class"] = cls_[:nreads]
         return out
 
+    # -- document votes (include/spumoni_docvote.h) ---------------------------
+    def votes_device(self, d_lengths, d_docs, d_offs, min_length, d_out=None, stream=None):
+        """One record per read (spv_vote: voters, top_doc, top_votes, second_votes) from the per-position lengths and
+        document ids of a query, on the device: returns d_out, an int32 tensor of shape (reads, 4).  int16 / uint16
+        tensors select the 16-bit form; both arrays have the same width."""
+        import torch
+
+        L = _spv()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_offs.numel() - 1
+        if d_lengths.element_size() != d_docs.element_size():
+            raise SpxError("d_lengths and d_docs must have the same width")
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 4), dtype=torch.int32, device=d_offs.device)
+        _check(L.spv_votes_device(self._h, _t_ptr(d_lengths), _t_ptr(d_docs), d_lengths.element_size() * 8, _t_ptr(d_offs),
+                                  nreads, min(d_lengths.numel(), d_docs.numel()), int(min_length), _t_ptr(d_out),
+                                  C.c_void_p(st.cuda_stream)))
+        return d_out
+
+    def assign_host(self, mode, seqs, offs, min_length, digest=None):
+        """spv_assign_batch: reads in, one record per read out -- a structured array (docvote.VOTE_DTYPE plus "values",
+        the read's positions after digestion).  digest: (kind, k, w) or None."""
+        from .docvote import VOTE_DTYPE
+
+        L = _spv()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=VOTE_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        _check(L.spv_assign_batch(self._h, mode, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length),
+                                  _np_ptr(rec), _np_ptr(vals)))
+        out = np.zeros(nreads, dtype=np.dtype(VOTE_DTYPE.descr + [("values", "<u8")]))
+        for f in VOTE_DTYPE.names:
+            out[f] = rec[f][:nreads]
+        out["values"] = vals[:nreads]
+        return out
+
+    def votes_stats(self) -> dict:
+        """Of the most recent votes_device / assign_host call: reads per kernel path, voting positions, kernel time."""
+        s = SpvVotesStats()
+        _check(_spv().spv_last_votes_stats(self._h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in SpvVotesStats._fields_}
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -503,6 +548,32 @@ def pad_seqs(seqs):
     padded = torch.zeros(((n + 3) // 4) * 4 + 32, dtype=torch.uint8, device=seqs.device)
     padded[:n] = seqs
     return padded
+
+
+# ---- the document votes (include/spumoni_docvote.h) -----------------------------------------------------------------
+DOCVOTE_EXPORTS = ["spv_votes_device", "spv_assign_batch", "spv_last_votes_stats"]
+_SPV_READY = False
+
+
+class SpvVotesStats(C.Structure):
+    _fields_ = [("reads_short", C.c_uint64), ("reads_medium", C.c_uint64), ("reads_long", C.c_uint64),
+                ("reads_empty", C.c_uint64), ("voting_positions", C.c_uint64), ("long_tiles", C.c_uint64),
+                ("kernel_ms", C.c_float)]
+
+
+def _spv() -> C.CDLL:
+    """The library with the spv_* argtypes set (on first use)."""
+    global _SPV_READY
+    L = lib()
+    if not hasattr(L, "spv_assign_batch"):
+        raise SpxError(f"{LIB_PATH} has no document votes (spv_assign_batch): there is no CPU fallback")
+    if not _SPV_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spv_votes_device.argtypes = [vp, vp, vp, i32, vp, u64, u64, u64, vp, vp]
+        L.spv_assign_batch.argtypes = [vp, i32, i32, u32, u32, vp, vp, u64, u64, vp, vp]
+        L.spv_last_votes_stats.argtypes = [vp, C.POINTER(SpvVotesStats)]
+        _SPV_READY = True
+    return L
 
 
 # ---- the index builder (include/spumoni_build.h) -------------------------------------------------------------------

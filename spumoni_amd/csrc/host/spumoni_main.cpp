@@ -388,13 +388,15 @@ static int dump_sdsl_main(int argc, char** argv) {
 }
 
 int build_main(int argc, char** argv);  // build_main.cpp
+int assign_main(int argc, char** argv);  // assign_main.cpp
 
 static int spumoni_usage() {
     std::fprintf(stderr, "SPUMONI has different sub-commands to run which can used as follows:\n");
     std::fprintf(stderr, "Usage: spumoni <command> [options]\n\n");
     std::fprintf(stderr, "Commands:\n");
     std::fprintf(stderr, "\tbuild\tbuilds the index needed to compute MS or PMLs for a specified reference.\n");
-    std::fprintf(stderr, "\trun\tcomputes MSs or PMLs for patterns against already built SPUMONI index.\n\n");
+    std::fprintf(stderr, "\trun\tcomputes MSs or PMLs for patterns against already built SPUMONI index.\n");
+    std::fprintf(stderr, "\tassign\tassigns each read to a document of an index built with a document array.\n\n");
     return 1;
 }
 
@@ -405,6 +407,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "\n\033[1m\033[31mSPUMONI version: %s \033[0m\n\n", SPUMONI_VERSION);
     if (argc > 1) {
         if (std::strcmp(argv[1], "build") == 0) return build_main(argc - 1, argv + 1);
+        if (std::strcmp(argv[1], "assign") == 0) return assign_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "run") == 0) {
             const int rc = run_main(argc - 1, argv + 1);
             if (std::getenv("SPX_FREE_TRACE")) std::fprintf(stderr, "[spumoni] main returns %d\n", rc);

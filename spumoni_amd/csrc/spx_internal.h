@@ -207,6 +207,17 @@ struct spx_index {
         void* p = nullptr;
         size_t cap = 0;
     } scratch[20], chunk_scr[9], digest_scr[NDIGSCR];  // host-buffer queries (8..19: text output); chunked walks and the length bits (under mu)
+    // document votes (spx_docvote.hip): counters, read lists and the long reads' tables (0..5, under mu), the two buffer
+    // sets of spv_assign_batch's pipeline (6.., under host_mu); the events around the vote kernels of the last call and
+    // what that call counted
+    static constexpr int NVOTESCR = 24;
+    Scratch vote_scr[NVOTESCR];
+    hipEvent_t ev_v0 = nullptr, ev_v1 = nullptr;
+    hipStream_t vote_stream = nullptr, assign_s[2] = {nullptr, nullptr};
+    bool have_votes = false, vote_pending = false;
+    uint64_t vote_acc[6] = {};
+    uint64_t vote_error = 0;
+    float vote_ms = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -270,6 +281,8 @@ inline int chunk_scratch(spx_index* ix, int slot, size_t bytes, void** out) {
     *out = sc.p;
     return SPX_OK;
 }
+// spx_docvote.hip: frees what the document votes hold of the device (spx_index_free)
+void release_votes(spx_index* ix);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
 int build_fat(spx_index* ix);
 // spx_walk.hip: MS text against the index: text[samples_start[k]] must be the head of run k
