@@ -829,30 +829,16 @@ __global__ void k_zero_tail(const uint64_t* out_offs, uint64_t nreads, uint8_t* 
 }  // namespace
 
 // The digestion's scratch: grow-only device buffers owned by the index (spx_index::digest_scr), like the chunked walk's.
-// (Round 4 took them from the stream-ordered allocator, which leaked them on every early return -- ADVICE r4 -- and needed a
-// release threshold on the device's default pool, a process-wide side effect; a pool of the handle's own was tried first and
-// hipMemPoolDestroy hung at exit once page-locked file mappings were in play: profiles/r05_cli_e2e_m_hang.txt.  Plain buffers
-// have neither problem.)  Calls on one handle are enqueued under its mutex; a call on another stream than the one before
-// waits for it (ev_dig), so the buffers are never shared by two calls in flight.
+// (The stream-ordered allocator leaked them on every early return and needed a process-wide release threshold; a pool of the
+// handle's own hung in hipMemPoolDestroy at exit: profiles/r05_cli_e2e_m_hang.txt.)  Calls on one handle are enqueued under its
+// mutex; a call on another stream than the one before waits for it (ev_dig): two calls in flight never share the buffers.
 namespace {
 struct DigestScratch {
     spx_index* ix;
     int n = 0;
-    explicit DigestScratch(spx_index* i) : ix(i) {}
     hipError_t get(void** out, size_t bytes) {
         if (n >= spx_index::NDIGSCR) return hipErrorOutOfMemory;
-        spx_index::Scratch& sc = ix->digest_scr[n++];
-        if (sc.cap < bytes) {
-            if (sc.p) (void)hipFree(sc.p);
-            sc.p = nullptr;
-            sc.cap = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&sc.p, want);
-            if (e != hipSuccess) return e;
-            sc.cap = want;
-        }
-        *out = sc.p;
-        return hipSuccess;
+        return ix->digest_scr[n++].grow(bytes, out);
     }
 };
 }  // namespace
@@ -910,7 +896,7 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
     a.counts = d_out_offs;
     a.out_offs = d_out_offs;
     a.out = d_out;
-    DigestScratch scr(ix);
+    DigestScratch scr{ix};
     if (ix->dig_used && ix->dig_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_dig, 0));
     struct Done {  // whatever way out: the next call on another stream waits for what this one enqueued
         spx_index* ix;
@@ -943,15 +929,9 @@ int launch_digest(spx_index* ix, int kind, uint32_t k, uint32_t w, const uint8_t
         };
         size_t tmp_bytes = 0;
         SPX_HIP(run(nullptr, tmp_bytes));
-        spx_index::Scratch& sc = ix->digest_scr[spx_index::NDIGSCR - 1];
-        if (sc.cap < tmp_bytes) {
-            if (sc.p) (void)hipFree(sc.p);
-            sc.p = nullptr;
-            sc.cap = 0;
-            SPX_HIP(hipMalloc(&sc.p, tmp_bytes + 4096));
-            sc.cap = tmp_bytes + 4096;
-        }
-        SPX_HIP(run(sc.p, tmp_bytes));
+        void* tmp = nullptr;
+        SPX_HIP(ix->digest_scr[spx_index::NDIGSCR - 1].grow(tmp_bytes, &tmp));
+        SPX_HIP(run(tmp, tmp_bytes));
         return SPX_OK;
     };
     // long reads of the default shape: a lane per chunk of 240 characters (k_digest_chunks)

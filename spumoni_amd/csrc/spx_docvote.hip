@@ -382,21 +382,6 @@ __global__ __launch_bounds__(256) void k_long_write(VoteArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.c->tiles = min64((uint64_t)a.c->n_tiles, a.tile_cap);
 }
 
-// grow-only device scratch of the votes (slots 0..5: callers hold ix->mu; 6..: callers hold ix->host_mu)
-int vote_scratch(spx_index* ix, int slot, size_t bytes, void** out) {
-    spx_index::Scratch& sc = ix->vote_scr[slot];
-    if (sc.cap < bytes) {
-        if (sc.p) (void)hipFree(sc.p);
-        sc.p = nullptr;
-        sc.cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        SPX_HIP(hipMalloc(&sc.p, want));
-        sc.cap = want;
-    }
-    *out = sc.p;
-    return SPX_OK;
-}
-
 // Enqueues the vote kernels on st.  long_values: an upper bound of the values in reads longer than MEDIUM_MAX (it sizes
 // their tables: 16 bytes per value).  Takes ix->mu.
 int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int value_bits, const uint64_t* d_offsets,
@@ -422,17 +407,17 @@ int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int 
     a.table_cap = a.long_cap ? std::min(long_values, total_values) : 0;
     void* p = nullptr;
     int rc;
-    if ((rc = vote_scratch(ix, 0, sizeof(VoteCounters), &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_COUNTERS].reserve(sizeof(VoteCounters), &p)) != SPX_OK) return rc;
     a.c = (VoteCounters*)p;
-    if ((rc = vote_scratch(ix, 1, a.medium_cap * 8, &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_MEDIUM].reserve(a.medium_cap * 8, &p)) != SPX_OK) return rc;
     a.medium_list = (uint64_t*)p;
-    if ((rc = vote_scratch(ix, 2, a.long_cap * 8, &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_LONG].reserve(a.long_cap * 8, &p)) != SPX_OK) return rc;
     a.long_list = (uint64_t*)p;
-    if ((rc = vote_scratch(ix, 3, a.tile_cap * 8, &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_TILES].reserve(a.tile_cap * 8, &p)) != SPX_OK) return rc;
     a.tile_list = (uint64_t*)p;
-    if ((rc = vote_scratch(ix, 4, a.long_cap * sizeof(LongAcc), &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_ACC].reserve(a.long_cap * sizeof(LongAcc), &p)) != SPX_OK) return rc;
     a.acc = (LongAcc*)p;
-    if ((rc = vote_scratch(ix, 5, a.table_cap * 16, &p)) != SPX_OK) return rc;
+    if ((rc = ix->vote_scr[spx_index::V_TABLE].reserve(a.table_cap * 16, &p)) != SPX_OK) return rc;
     a.table = (uint4*)p;
     // the counters, lists and events are the index's: a call on another stream waits for the one before
     if (ix->have_votes && ix->vote_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_v1, 0));
@@ -473,7 +458,7 @@ int votes_collect(spx_index* ix) {
     SPX_HIP(hipSetDevice(ix->device));
     SPX_HIP(hipEventSynchronize(ix->ev_v1));
     VoteCounters c;
-    SPX_HIP(hipMemcpy(&c, ix->vote_scr[0].p, sizeof c, hipMemcpyDeviceToHost));
+    SPX_HIP(hipMemcpy(&c, ix->vote_scr[spx_index::V_COUNTERS].p, sizeof c, hipMemcpyDeviceToHost));
     float ms = 0;
     SPX_HIP(hipEventElapsedTime(&ms, ix->ev_v0, ix->ev_v1));
     const unsigned long long v[6] = {c.reads_short, c.reads_medium, c.reads_long, c.reads_empty, c.voting, c.tiles};
@@ -649,12 +634,13 @@ int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint3
         std::vector<uint64_t> h_off, h_dig_off;
     } set[2];
     for (int b = 0; b < 2 && (b == 0 || cut.size() > 2); ++b) {
-        const size_t sizes[8] = {raw_bytes, (worst_reads + 1) * 8, dig_bytes, digest_kind ? (worst_reads + 1) * 8 : 0,
+        constexpr int NSET = spx_index::V_SET_STRIDE;
+        const size_t sizes[NSET] = {raw_bytes, (worst_reads + 1) * 8, dig_bytes, digest_kind ? (worst_reads + 1) * 8 : 0,
                                  (worst_chars + 16) * width, (worst_chars + 16) * width,
                                  mode == SPX_MODE_MS ? (worst_chars + 2) * 8 : 0, (worst_reads + 1) * sizeof(spv_vote)};
-        void* p[8] = {};
-        for (int i = 0; i < 8; ++i)
-            if (sizes[i] && (rc = vote_scratch(ix, 6 + b * 8 + i, sizes[i], &p[i])) != SPX_OK) return rc;
+        void* p[NSET] = {};
+        for (int i = 0; i < NSET; ++i)
+            if (sizes[i] && (rc = ix->vote_scr[spx_index::V_SET0 + b * NSET + i].reserve(sizes[i], &p[i])) != SPX_OK) return rc;
         set[b].raw = (uint8_t*)p[0];
         set[b].off = (uint64_t*)p[1];
         set[b].dig = (uint8_t*)p[2];
@@ -664,13 +650,7 @@ int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint3
         set[b].ptr = (uint64_t*)p[6];
         set[b].out = (spv_vote*)p[7];
     }
-    // every way out that is not SPX_OK waits for the copies that still read or write the caller's memory
-    struct Quiet {
-        bool ok = false;
-        ~Quiet() {
-            if (!ok) (void)hipDeviceSynchronize();
-        }
-    } quiet;
+    QuietOnError quiet(nullptr, true);  // (two streams: a failed call waits for the device)
     const size_t npieces = cut.size() - 1;
     auto copy_in = [&](size_t c) -> int {
         Set& s = set[c & 1];
@@ -738,8 +718,7 @@ int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint3
         if ((rc = run(c)) != SPX_OK) return rc;
     }
     if ((rc = finish(npieces - 1)) != SPX_OK) return rc;
-    quiet.ok = true;
-    return SPX_OK;
+    return quiet.done(SPX_OK);
 }
 
 }  // extern "C"

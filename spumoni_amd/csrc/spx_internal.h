@@ -23,6 +23,28 @@ int select_device(int device);
         if (e_ != hipSuccess) return spx::hip_fail(e_, #call, __FILE__, __LINE__); \
     } while (0)
 
+// The host-buffer entry points enqueue their copies on streams of the handle and leave early on any error after that.  A copy
+// that is still reading the caller's inputs (or writing its outputs) when the call has already failed would leave work in
+// flight on memory the caller may free: every way out that is not through done(SPX_OK) waits first -- for the stream, or
+// (device_wide: the pipelines run on several streams of the handle) for the device.
+struct QuietOnError {
+    hipStream_t st;
+    bool device_wide;
+    bool ok = false;
+    explicit QuietOnError(hipStream_t s, bool wide = false) : st(s), device_wide(wide) {}
+    int done(int rc) {
+        ok = rc == SPX_OK;
+        return rc;
+    }
+    ~QuietOnError() {
+        if (ok) return;
+        if (device_wide)
+            (void)hipDeviceSynchronize();
+        else
+            (void)hipStreamSynchronize(st);
+    }
+};
+
 // counters written by the walk kernels (one instance per index, device memory)
 struct WalkCounters {
     unsigned long long reserved0;
@@ -176,7 +198,7 @@ struct spx_index {
     // host-buffer queries (spx_query_batch*, spx_digest_*batch, spx_query_text_*) run on a stream of the handle's own, so
     // that two handles on one device -- the CLI's two workers per device -- overlap one's copies with the other's kernels
     hipStream_t ctx_stream = nullptr;
-    // the digestion's scratch (spx_digest.hip: grow-only, under mu), the stream its last call ran on and what that call enqueued
+    // the digestion's scratch slots (digest_scr below), the stream its last call ran on and what that call enqueued
     static constexpr int NDIGSCR = 15;
     hipEvent_t ev_dig = nullptr;
     hipStream_t dig_stream = nullptr;
@@ -202,16 +224,45 @@ struct spx_index {
     hipStream_t pipe_s[3] = {nullptr, nullptr, nullptr};
     hipEvent_t pipe_in[PIPE_CHUNKS] = {}, pipe_k[PIPE_CHUNKS] = {};
     std::mutex mu;       // device-buffer queries / options
-    std::mutex host_mu;  // host-buffer queries (own the scratch below)
+    std::mutex host_mu;  // host-buffer queries (taken before mu)
+    // Device scratch owned by the index: grow-only, so that no call pays a hipMalloc / hipFree of its own.  A buffer that grows
+    // is freed first, which synchronises the whole device: a pipeline sizes its slots for the worst case before it starts.
     struct Scratch {
         void* p = nullptr;
         size_t cap = 0;
-    } scratch[20], chunk_scr[9], digest_scr[NDIGSCR];  // host-buffer queries (8..19: text output); chunked walks and the length bits (under mu)
-    // document votes (spx_docvote.hip): counters, read lists and the long reads' tables (0..5, under mu), the two buffer
-    // sets of spv_assign_batch's pipeline (6.., under host_mu); the events around the vote kernels of the last call and
-    // what that call counted
-    static constexpr int NVOTESCR = 24;
-    Scratch vote_scr[NVOTESCR];
+        hipError_t grow(size_t bytes, void** out) {  // the one growth rule: a quarter and 256 bytes of head-room
+            if (cap < bytes) {
+                if (p) (void)hipFree(p);
+                p = nullptr;
+                cap = 0;
+                const size_t want = bytes + bytes / 4 + 256;
+                const hipError_t e = hipMalloc(&p, want);
+                if (e != hipSuccess) return e;
+                cap = want;
+            }
+            *out = p;
+            return hipSuccess;
+        }
+        int reserve(size_t bytes, void** out) {
+            SPX_HIP(grow(bytes, out));
+            return SPX_OK;
+        }
+    };
+    // host-buffer queries (under host_mu).  The walk reads S_SEQ; under digestion the caller's reads go to S_RAW and S_SEQ
+    // holds what the digestion made of them (reads_slot).  S_GAP .. S_TEXT: text output, + i for the stream
+    enum { S_SEQ, S_OFFS, S_LEN, S_PTR, S_DOC, S_CLASS, S_RAW, S_DIG_OFFS, S_GAP, S_SCAN,
+           S_LINE_BYTES, S_LINE_START = S_LINE_BYTES + 3, S_TEXT = S_LINE_START + 3, S_COUNT = S_TEXT + 3 };
+    static constexpr int reads_slot(int digest_kind) { return digest_kind ? S_RAW : S_SEQ; }
+    Scratch scratch[S_COUNT];
+    // chunked walks and, C_LEN_BITS, the PML reset bits of every walk (under mu)
+    enum { C_DESC, C_ENDS, C_SEAMS, C_CKPT, C_FLAGS, C_FAIL, C_CNT, C_CUB, C_LEN_BITS, C_COUNT };
+    Scratch chunk_scr[C_COUNT];
+    Scratch digest_scr[NDIGSCR];  // spx_digest.hip (under mu): handed out in the order asked for, the last one to the scans
+    // document votes (spx_docvote.hip): counters, read lists and the long reads' tables (under mu), then the two buffer
+    // sets of spv_assign_batch's pipeline, V_SET_STRIDE slots each (under host_mu); the events around the vote kernels
+    // of the last call and what that call counted
+    enum { V_COUNTERS, V_MEDIUM, V_LONG, V_TILES, V_ACC, V_TABLE, V_SET0, V_SET_STRIDE = 8, V_COUNT = V_SET0 + 2 * V_SET_STRIDE };
+    Scratch vote_scr[V_COUNT];
     hipEvent_t ev_v0 = nullptr, ev_v1 = nullptr;
     hipStream_t vote_stream = nullptr, assign_s[2] = {nullptr, nullptr};
     bool have_votes = false, vote_pending = false;
@@ -267,20 +318,11 @@ inline void bind_view(spx_index* ix) {
     v.text = ix->text;
     v.n_text = ix->n_text;
 }
-// grow-only device scratch of the chunked walk (callers hold ix->mu)
-inline int chunk_scratch(spx_index* ix, int slot, size_t bytes, void** out) {
-    spx_index::Scratch& sc = ix->chunk_scr[slot];
-    if (sc.cap < bytes) {
-        if (sc.p) (void)hipFree(sc.p);
-        sc.p = nullptr;
-        sc.cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        SPX_HIP(hipMalloc(&sc.p, want));
-        sc.cap = want;
-    }
-    *out = sc.p;
-    return SPX_OK;
-}
+// spx_api.hip: the stream of the handle's host-buffer queries (created on first use; callers hold host_mu), waiting for it
+// (spinning or, "blocking_sync", asleep), and what every index carries however its arrays came to be
+int ctx_stream_of(spx_index* ix, hipStream_t* out);
+int ctx_wait(spx_index* ix, hipStream_t st);
+int init_runtime(spx_index* ix);
 // spx_docvote.hip: frees what the document votes hold of the device (spx_index_free)
 void release_votes(spx_index* ix);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
@@ -302,6 +344,7 @@ int launch_ms_extend(spx_index* ix, const BatchArgs& args, hipStream_t stream);
 // PML lengths through one bit per character: prepare_len_mask before the walk (sets args.len_mask; nothing
 // to do for MS or a classification-only query), launch_len_expand after it
 int prepare_len_mask(spx_index* ix, int mode, BatchArgs& args);
+inline uint64_t len_mask_pairs(uint64_t chars, uint64_t reads) { return (chars >> 7) + reads + 2; }  // 16-byte pairs of the bits
 int launch_len_expand(spx_index* ix, const BatchArgs& args, hipStream_t stream);
 // long-read batches: the chunked walk (returns SPX_OK and sets *done = false when the batch does not
 // qualify and the plain walk should run)

@@ -1632,14 +1632,14 @@ int launch_walk_chunked(spx_index* ix, int mode, const BatchArgs& args, uint64_t
     void *p_desc, *p_ends, *p_seams, *p_ckpt, *p_flags, *p_fail, *p_cnt, *p_start, *p_cub;
     const size_t fail_words = args.nreads + 1 + 16;  // per read, then the per-round counters
     int rc;
-    if ((rc = chunk_scratch(ix, 0, bound * sizeof(ChunkDesc), &p_desc)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 1, 2 * (bound + 1) * sizeof(WalkState), &p_ends)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 2, bound * sizeof(SeamRec), &p_seams)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 3, nck * sizeof(WalkState), &p_ckpt)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 4, total_chars + 32, &p_flags)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 5, fail_words * 4, &p_fail)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 6, (args.nreads + 2) * 8 * 3 + 16, &p_cnt)) != SPX_OK) return rc;
-    if ((rc = chunk_scratch(ix, 7, cub_bytes + 256, &p_cub)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_DESC].reserve(bound * sizeof(ChunkDesc), &p_desc)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_ENDS].reserve(2 * (bound + 1) * sizeof(WalkState), &p_ends)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_SEAMS].reserve(bound * sizeof(SeamRec), &p_seams)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_CKPT].reserve(nck * sizeof(WalkState), &p_ckpt)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_FLAGS].reserve(total_chars + 32, &p_flags)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_FAIL].reserve(fail_words * 4, &p_fail)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_CNT].reserve((args.nreads + 2) * 8 * 3 + 16, &p_cnt)) != SPX_OK) return rc;
+    if ((rc = ix->chunk_scr[spx_index::C_CUB].reserve(cub_bytes + 256, &p_cub)) != SPX_OK) return rc;
     uint64_t* cnt = (uint64_t*)p_cnt;
     uint64_t* nchunks = cnt + (args.nreads + 1);      // one counter
     p_start = cnt + (args.nreads + 2);                // nreads + 1 entries... laid out after the counter
@@ -1788,8 +1788,8 @@ int prepare_len_mask(spx_index* ix, int mode, BatchArgs& args) {
     args.len_mask = nullptr;
     if (mode != SPX_MODE_PML || args.out_lengths == nullptr || args.nreads == 0) return SPX_OK;
     void* p = nullptr;
-    const uint64_t pairs = (args.total_chars >> 7) + args.nreads + 2;
-    const int rc = chunk_scratch(ix, 8, pairs * 16, &p);
+    const uint64_t pairs = len_mask_pairs(args.total_chars, args.nreads);
+    const int rc = ix->chunk_scr[spx_index::C_LEN_BITS].reserve(pairs * 16, &p);
     if (rc != SPX_OK) return rc;
     args.len_mask = (uint64_t*)p;
     args.len_mask_pairs = pairs;

@@ -2,7 +2,7 @@
 // One worker's super-batch is: a host-to-device copy (32 MB of reads, page-locked buffer), kernels (~1 ms), a device-to-host copy
 // (75 MB of text) into page-locked memory -- the output file's mapping (hipHostRegister) or a hipHostMalloc buffer.  Two workers
 // on two non-blocking streams, each from a thread of its own, each synchronising its own stream after every step the way the
-// C-ABI's host-buffer entry points do (spx_api.hip: hipMemcpyAsync + hipStreamSynchronize on the handle's ctx_stream).
+// C-ABI's host-buffer entry points do (spx_query.hip: hipMemcpyAsync + hipStreamSynchronize on the handle's ctx_stream).
 // Prints the time per super-batch of ONE worker alone and of two at once: 2 x alone = the device serialises them,
 // ~max(copy-out, copy-in + kernels) = it overlaps them.
 //   hipcc --offload-arch=gfx950 -O2 -pthread tools/overlap_hip.hip -o tools/overlap_hip.bin ; tools/overlap_hip.bin /dev/shm/x
