@@ -494,6 +494,68 @@ class Index:
         _check(_spv().spv_last_votes_stats(self._h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SpvVotesStats._fields_}
 
+    # -- matches (include/spumoni_mems.h) --------------------------------------
+    def mems_device(self, d_lengths, d_pointers, d_offs, min_length, d_docs=None, capacity=None, d_match_offsets=None,
+                    d_out=None, d_out_docs=None, stream=None):
+        """The reported match starts of every read (spm_match: ref_pos u64, read_pos u32, length u32) from the MS lengths
+        and pointers of a query, on the device: returns (d_match_offsets int64[reads + 1], d_records int32 (capacity, 4)
+        [, d_docs int32]).  int16 / uint16 lengths select the 16-bit form (d_docs has the same width).  capacity None: a
+        first call counts, the host reads the count, a second call writes that many records; given: one call, records
+        of rank >= capacity are left out (mems_stats() says so)."""
+        import torch
+
+        L = _spm()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_offs.numel() - 1
+        if d_docs is not None and d_lengths.element_size() != d_docs.element_size():
+            raise SpxError("d_lengths and d_docs must have the same width")
+        if d_match_offsets is None:
+            d_match_offsets = torch.empty(max(nreads, 0) + 1, dtype=torch.int64, device=d_offs.device)
+        total = d_lengths.numel()
+
+        def call(cap, out, out_docs):
+            _check(L.spm_mems_device(self._h, _t_ptr(d_lengths), d_lengths.element_size() * 8, _t_ptr(d_pointers), _t_ptr(d_docs),
+                                     _t_ptr(d_offs), nreads, total, int(min_length), _t_ptr(d_match_offsets), _t_ptr(out), cap,
+                                     _t_ptr(out_docs), C.c_void_p(st.cuda_stream)))
+
+        if capacity is None:
+            call(0, None, None)
+            st.synchronize()
+            capacity = int(d_match_offsets[-1].item())
+        if d_out is None:
+            d_out = torch.empty((capacity, 4), dtype=torch.int32, device=d_offs.device)
+        if d_docs is not None and d_out_docs is None:
+            d_out_docs = torch.empty(capacity, dtype=torch.int32, device=d_offs.device)
+        call(capacity, d_out, d_out_docs)
+        return (d_match_offsets, d_out) if d_docs is None else (d_match_offsets, d_out, d_out_docs)
+
+    def mems_host(self, seqs, offs, min_length, digest=None, want_docs=False):
+        """spm_mems_begin / _fetch: reads in, (match_offsets uint64[reads + 1], records mems.MATCH_DTYPE[, docs uint32], values
+        uint64[reads]) out; values = the read's positions after digestion.  digest: (kind, k, w) or None."""
+        from .mems import MATCH_DTYPE
+
+        L = _spm()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        moffs = np.zeros(max(nreads, 0) + 1, dtype=np.uint64)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        n = C.c_uint64()
+        _check(L.spm_mems_begin(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                _np_ptr(moffs), _np_ptr(vals), C.byref(n)))
+        rec = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
+        docs = np.zeros(max(n.value, 1), dtype=np.uint32) if want_docs else None
+        _check(L.spm_mems_fetch(self._h, _np_ptr(rec), _np_ptr(docs)))
+        out = (moffs, rec[: n.value]) + ((docs[: n.value],) if want_docs else ())
+        return out + (vals[:nreads],)
+
+    def mems_stats(self) -> dict:
+        """Of the most recent mems_device / mems_host call: values, matches, records written, longest length, kernel time."""
+        s = SpmMemsStats()
+        _check(_spm().spm_last_mems_stats(self._h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in SpmMemsStats._fields_}
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -573,6 +635,32 @@ def _spv() -> C.CDLL:
         L.spv_assign_batch.argtypes = [vp, i32, i32, u32, u32, vp, vp, u64, u64, vp, vp]
         L.spv_last_votes_stats.argtypes = [vp, C.POINTER(SpvVotesStats)]
         _SPV_READY = True
+    return L
+
+
+# ---- the matches (include/spumoni_mems.h) ---------------------------------------------------------------------------
+MEMS_EXPORTS = ["spm_mems_device", "spm_mems_begin", "spm_mems_fetch", "spm_last_mems_stats"]
+_SPM_READY = False
+
+
+class SpmMemsStats(C.Structure):
+    _fields_ = [("values", C.c_uint64), ("matches", C.c_uint64), ("written", C.c_uint64), ("longest", C.c_uint64),
+                ("kernel_ms", C.c_float)]
+
+
+def _spm() -> C.CDLL:
+    """The library with the spm_* argtypes set (on first use)."""
+    global _SPM_READY
+    L = lib()
+    if not hasattr(L, "spm_mems_begin"):
+        raise SpxError(f"{LIB_PATH} has no match kernels (spm_mems_begin): there is no CPU fallback")
+    if not _SPM_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spm_mems_device.argtypes = [vp, vp, i32, vp, vp, vp, u64, u64, u64, vp, vp, u64, vp, vp]
+        L.spm_mems_begin.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, vp, vp, C.POINTER(u64)]
+        L.spm_mems_fetch.argtypes = [vp, vp, vp]
+        L.spm_last_mems_stats.argtypes = [vp, C.POINTER(SpmMemsStats)]
+        _SPM_READY = True
     return L
 
 

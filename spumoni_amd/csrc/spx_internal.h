@@ -269,6 +269,18 @@ struct spx_index {
     uint64_t vote_acc[6] = {};
     uint64_t vote_error = 0;
     float vote_ms = 0;
+    // matches (spx_mems.hip): counters, the bitmap of reported starts, its prefix sums and the scan's space (under mu),
+    // then spm_mems_begin's buffers (under host_mu); the events around the count and the write kernels of the last
+    // call, what that call counted, and the records that wait for spm_mems_fetch
+    enum { M_COUNTERS, M_BITS, M_PREFIX, M_CUB, M_RAW, M_OFFS, M_DIG, M_DIG_OFFS, M_LEN, M_PTR, M_DOC, M_MOFFS, M_OUT,
+           M_OUT_DOCS, M_COUNT };
+    Scratch mems_scr[M_COUNT];
+    hipEvent_t ev_m[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t mems_stream = nullptr;
+    bool have_mems = false, mems_pending = false, mems_ready = false, mems_ready_docs = false;
+    uint64_t mems_capacity = 0, mems_ready_n = 0;
+    uint64_t mems_acc[4] = {};  // values, matches, longest, error bits
+    float mems_ms = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -325,6 +337,8 @@ int ctx_wait(spx_index* ix, hipStream_t st);
 int init_runtime(spx_index* ix);
 // spx_docvote.hip: frees what the document votes hold of the device (spx_index_free)
 void release_votes(spx_index* ix);
+// spx_mems.hip: the same for the matches
+void release_mems(spx_index* ix);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
 int build_fat(spx_index* ix);
 // spx_walk.hip: MS text against the index: text[samples_start[k]] must be the head of run k
