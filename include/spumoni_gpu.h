@@ -189,8 +189,14 @@ int spx_index_describe(const spx_index *ix, char *buf, size_t cap);
  *                 writing the per-character values (the report's columns only)
  *   out_pointers  MS pointers (MS mode only)
  *   out_docs      document ids (index must have been built with doc arrays)
- *   out_class     nreads entries, bin-max classifier over out_lengths' values
- *                 (bin_width in [1, ..]; ignored when out_class is NULL)
+ *   out_class     nreads entries, bin-max classifier over out_lengths' values.
+ *                 bin_width: any value in [1, 2^64 - 1], 0 is refused.  A read
+ *                 has fewer than 2^32 values, so every width of 2^32 - 1 or
+ *                 more means "the whole read is one bin" (the library takes
+ *                 such a width as 2^32 - 1).  max_value_thr: any uint64_t; 0
+ *                 puts every bin above, a value above every length (they are
+ *                 below 2^32) every bin below -- also on the 16-bit entry
+ *                 points.  Both are ignored when out_class is NULL.
  * Host-buffer form: copies in, runs, copies out, returns when done (large
  * batches as a pipeline of chunks, so that the copies overlap the kernels; the
  * kernel time spx_last_walk_stats reports then spans that pipeline).           */

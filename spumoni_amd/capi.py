@@ -179,6 +179,17 @@ def _t_ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _class_buffer(classify, class_out, nreads):
+    """Where a host query's class records go: nowhere, a fresh array, or the array the caller gave."""
+    if not classify:
+        return None
+    if class_out is None:
+        return np.zeros(max(nreads, 1), dtype=CLASS_DTYPE)
+    if class_out.dtype != CLASS_DTYPE or class_out.ndim != 1 or class_out.size < nreads or not class_out.flags.c_contiguous:
+        raise SpxError("class_out must be a contiguous CLASS_DTYPE array of nreads entries or more")
+    return class_out
+
+
 class Index:
     """An spx_index on one GPU."""
 
@@ -302,8 +313,9 @@ class Index:
         _check(lib().spx_set_option(self._h, key.encode(), value))
 
     # -- queries, host buffers (numpy) --------------------------------------
-    def query_host(self, mode, seqs, offs, want_lengths=True, want_docs=False, classify=None, bits=32):
-        """bits=16: the 16-bit entry point (uint16 lengths / docs; reads shorter than 65536)."""
+    def query_host(self, mode, seqs, offs, want_lengths=True, want_docs=False, classify=None, bits=32, class_out=None):
+        """bits=16: the 16-bit entry point (uint16 lengths / docs; reads shorter than 65536).  class_out: the caller's
+        CLASS_DTYPE array for the class records (nreads entries at least; tests pass a slice of a larger, fenced one)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         nreads = offs.size - 1
@@ -312,7 +324,7 @@ class Index:
         lens = np.zeros(max(tot, 1) + 8, dtype=vt) if want_lengths else None  # PML: None + classify = report only
         ptrs = np.zeros(max(tot, 1), dtype=np.uint64) if mode == SPX_MODE_MS else None
         docs = np.zeros(max(tot, 1) + 8, dtype=vt) if want_docs else None
-        cls_ = np.zeros(max(nreads, 1), dtype=CLASS_DTYPE) if classify else None
+        cls_ = _class_buffer(classify, class_out, nreads)
         bw, thr = classify if classify else (0, 0)
         fn = lib().spx_query_batch16 if bits == 16 else lib().spx_query_batch
         _check(fn(self._h, mode, _np_ptr(seqs), _np_ptr(offs), nreads, _np_ptr(lens),
@@ -328,7 +340,8 @@ class Index:
             out["class"] = cls_[:nreads]
         return out
 
-    def query_text(self, mode, seqs, offs, gap=None, streams=SPX_TEXT_LENGTHS, digest=(0, 0, 0), classify=None):
+    def query_text(self, mode, seqs, offs, gap=None, streams=SPX_TEXT_LENGTHS, digest=(0, 0, 0), classify=None,
+                   class_out=None):
         """The vectors as the text of the output files (spx_query_text_begin / _fetch).  Returns
         {"text": [bytes | None] * 3, "line_start": [uint64 array | None] * 3, "class": ...}; stream i = lengths,
         pointers, document ids."""
@@ -336,7 +349,7 @@ class Index:
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         nreads = offs.size - 1
         g = None if gap is None else np.ascontiguousarray(gap, dtype=np.uint32)
-        cls_ = np.zeros(max(nreads, 1), dtype=CLASS_DTYPE) if classify else None
+        cls_ = _class_buffer(classify, class_out, nreads)
         bw, thr = classify if classify else (0, 0)
         nbytes = (C.c_uint64 * 3)()
         _check(lib().spx_query_text_begin(self._h, mode, digest[0], digest[1], digest[2], _np_ptr(seqs), _np_ptr(offs), nreads,
@@ -359,14 +372,16 @@ class Index:
 
     # -- queries, device buffers (torch tensors on self.device) -------------
     def query_device(self, mode, d_seqs, d_offs, total_chars, d_lengths=None, d_pointers=None, d_docs=None,
-                     d_class=None, bin_width=0, max_value_thr=0, stream=None):
+                     d_class=None, bin_width=0, max_value_thr=0, stream=None, narrow=None):
         """Enqueue on `stream` (a torch.cuda.Stream or None = torch's current stream).  int16 / uint16
-        tensors for d_lengths / d_docs select the 16-bit entry point."""
+        tensors for d_lengths / d_docs select the 16-bit entry point; narrow=True / False says so where neither is given
+        (PML classes alone)."""
         import torch
 
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         nreads = d_offs.numel() - 1
-        narrow = any(t is not None and t.element_size() == 2 for t in (d_lengths, d_docs))
+        if narrow is None or d_lengths is not None or d_docs is not None:
+            narrow = any(t is not None and t.element_size() == 2 for t in (d_lengths, d_docs))
         fn = lib().spx_query_batch_device16 if narrow else lib().spx_query_batch_device
         _check(fn(
             self._h, mode, _t_ptr(d_seqs), _t_ptr(d_offs), nreads, total_chars, _t_ptr(d_lengths),
@@ -421,7 +436,8 @@ class Index:
                   C.c_void_p(st.cuda_stream)))
         return work[1], work
 
-    def digest_query_host(self, mode, kind, k, w, seqs, offs, want_lengths=True, want_docs=False, classify=None):
+    def digest_query_host(self, mode, kind, k, w, seqs, offs, want_lengths=True, want_docs=False, classify=None,
+                          class_out=None):
         """digest + query in one call (the reference's per-read loop body, for a batch)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -432,7 +448,7 @@ class Index:
         lens = np.zeros(cap, dtype=np.uint32) if want_lengths else None
         ptrs = np.zeros(cap, dtype=np.uint64) if mode == SPX_MODE_MS else None
         docs = np.zeros(cap, dtype=np.uint32) if want_docs else None
-        cls_ = np.zeros(max(nreads, 1), dtype=CLASS_DTYPE) if classify else None
+        cls_ = _class_buffer(classify, class_out, nreads)
         bw, thr = classify if classify else (0, 0)
         _check(lib().spx_digest_query_batch(self._h, mode, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads,
                                             _np_ptr(out_offs), cap, _np_ptr(lens), _np_ptr(ptrs), _np_ptr(docs),

@@ -245,6 +245,10 @@ static BatchArgs make_batch_args(spx_index* ix, const uint8_t* d_seqs, const uin
     a.out_lengths = lengths;
     a.out_pointers = pointers;
     a.out_docs = docs;
+    // A read has fewer than 2^32 values, so every width from 2^32 - 1 on is "one bin": m / w < 1 for w > m, and
+    // m = w = 2^32 - 1 is one bin too.  The walks keep the width in 32 bits (registers of the hot loop); clamped here,
+    // before the magic number is derived from it, every kernel sees the same width.
+    if (bin_width > 0xffffffffull) bin_width = 0xffffffffull;
     a.bin_width = bin_width;
     a.bin_magic = bin_width > 1 ? (uint64_t)(~0ull / bin_width) + 1 : 0;
     a.max_value_thr = max_value_thr;

@@ -165,3 +165,97 @@ def walk_offsets(orc, raw, seqs, offs, nreads=40):
             if pos < n:
                 out.append(pos - int(starts[np.searchsorted(starts, pos, side="right") - 1]))
     return np.asarray(out, dtype=np.uint64)
+
+
+# ---- the bin-max classifier over bin widths and thresholds (test_classify_cpu.py, test_gpu_classify.py) ----
+CLASSIFY_LENGTHS = [0, 1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 511, 512, 513, 1000,
+                    1023, 1024, 1025]
+# w - 1, w, w + 1 (and 2 w - 1, 2 w, 2 w + 1, as a width or through the read lengths above) for the sizes the kernels count
+# in: 8 values per 16-byte load, the 64-character flush word of k_walk_fast, the tiles of 256 / 512 values of
+# k_classify_tiles; a read's length +- 1 (1000); 2^16 and 2^32 and their neighbours; one bin whatever the read (2^40, 2^63)
+CLASSIFY_WIDTHS = [1, 2, 3, 7, 8, 9, 63, 64, 65, 128, 150, 255, 256, 257, 511, 512, 513, 999, 1000, 1001, 65535, 65536, 1 << 31,
+                   (1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 32) + 7, (1 << 32) + 64, 1 << 40, 1 << 63]
+
+
+def classify_thresholds(lengths):
+    """0, 1, the median and the maximum of `lengths`, max + 1, and the values around the widths an implementation may have
+    narrowed the threshold to (16, 32 and 64 bits)."""
+    v = np.sort(np.asarray(lengths, dtype=np.uint64))
+    med, mx = int(v[v.size // 2]), int(v[-1])
+    out = []
+    for t in (0, 1, med, mx, mx + 1, 65535, 65536, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 64) - 1):
+        if t not in out:
+            out.append(t)
+    return out, med, mx
+
+
+def classify_bins(m, w):
+    """The rule of compute_ms_pml.cpp:969-995 in plain integers: the bins [k w, (k + 1) w) of a read of m values, the last
+    one taking the rest when fewer than w values would remain, and one bin at least for m > 0."""
+    if m == 0:
+        return []
+    nb = max(1, m // w)
+    return [(k * w, (k + 1) * w if k + 1 < nb else m) for k in range(nb)]
+
+
+def classify_rule(lengths, offs, w, thr):
+    """(above, below, sum_max) per read as lists of Python integers: a bin is above iff its maximum >= thr."""
+    vals = [int(v) for v in lengths]
+    out = []
+    for q in range(len(offs) - 1):
+        base, m = int(offs[q]), int(offs[q + 1]) - int(offs[q])
+        mx = [max(vals[base + lo: base + hi]) for lo, hi in classify_bins(m, w)]
+        above = sum(1 for v in mx if v >= thr)
+        out.append((above, len(mx) - above, sum(mx)))
+    return out
+
+
+def classify_case(seed=5, n=6000, random_reads=30):
+    """(raw, text, seqs, offs): an index with text, SA samples and documents over `n` characters, and reads of every length
+    in CLASSIFY_LENGTHS twice -- once cut from the text with a few substitutions (long matches: large values), once random
+    letters (values of a few units) -- plus `random_reads` reads of 1 .. 1200 characters, half of either kind, with runs of
+    empty reads at the front, in the middle and at the end."""
+    letters = list(b"ACGT")
+    raw, text = real_case(seed, n, letters, ndocs=3)
+    rng = np.random.default_rng(seed + 100)
+    lens = [(m, kind) for m in CLASSIFY_LENGTHS for kind in (0, 1)]
+    # (of the random lengths the longer half is cut from the text: most characters then carry large values, the median
+    # lies among them, and a stretch of random letters inside such a read is a run of bins below it)
+    extra = sorted(int(x) for x in rng.integers(1, 1201, size=random_reads))
+    lens += [(m, 1 if q < random_reads // 2 else 0) for q, m in enumerate(extra)]
+    order = rng.permutation(len(lens))
+    lens = [lens[i] for i in order]
+    half = len(lens) // 2
+    lens = [(0, 0)] * 3 + lens[:half] + [(0, 0)] * 3 + lens[half:] + [(0, 0)] * 3
+    reads = []
+    for m, kind in lens:
+        if kind == 0 and m:
+            s = int(rng.integers(0, text.size - m))
+            rd = text[s: s + m].copy()
+            for _ in range(m // 150):  # a substitution every 150 characters or so: the values fall and rise inside a read
+                rd[rng.integers(0, m)] = letters[rng.integers(0, 4)]
+            if m >= 400:  # and a stretch of random letters, longer than two bins of 64
+                at = int(rng.integers(0, m - 160))
+                rd[at: at + 160] = np.asarray(letters, dtype=np.uint8)[rng.integers(0, 4, size=160)]
+        else:
+            rd = np.asarray(letters, dtype=np.uint8)[rng.integers(0, 4, size=m)]
+        reads.append(rd.astype(np.uint8))
+    offs = np.concatenate([[0], np.cumsum([r.size for r in reads])]).astype(np.int64)
+    return raw, text, np.concatenate(reads), offs
+
+
+def classify_conditions(oracle_mod, lengths, offs):
+    """What a classifier test needs from its batch, asserted on the oracle's answers so that it cannot pass vacuously:
+    at the median threshold and bins of 8 and of 64 some read has bins above and bins below at once; some read has more
+    than one bin and a length that is no multiple of the width; nothing is below threshold 0, nothing above max + 1."""
+    _, med, mx = classify_thresholds(lengths)
+    m = np.diff(np.asarray(offs, dtype=np.int64))
+    for w in (8, 64):
+        _, a, b, _ = oracle_mod.classify(lengths, offs, w, med)
+        assert ((a > 0) & (b > 0)).any(), (w, med)
+        assert ((a + b > 1) & (m % w != 0)).any(), w
+    _, a, b, _ = oracle_mod.classify(lengths, offs, 8, 0)
+    assert a.any() and not b.any()
+    _, a, b, _ = oracle_mod.classify(lengths, offs, 8, mx + 1)
+    assert b.any() and not a.any()
+    return med, mx

@@ -39,6 +39,13 @@ got = ix.query_host(capi.SPX_MODE_MS, seqs, offs, want_docs=True, classify=(60, 
 assert np.array_equal(got["pointers"], ms["pointers"]) and np.array_equal(got["lengths"], ms["lengths"]) and np.array_equal(got["docs"], ms["docs"])
 f2, a2, b2, s2 = oracle.classify(ms["lengths"], offs, 60, 6)
 assert np.array_equal(got["class"]["above"], a2) and np.array_equal(got["class"]["sum_max"], s2)
+# class records into the caller's array (a slice of a larger one), 64-bit width and threshold
+mine = np.zeros(offs.size + 7, dtype=capi.CLASS_DTYPE)
+mine["above"] = 77
+got = ix.query_host(capi.SPX_MODE_PML, seqs, offs, classify=((1 << 32) + 1, 1 << 32), class_out=mine[4:])
+a3 = oracle.classify(pml, offs, (1 << 32) + 1, 1 << 32)
+assert got["class"].base is not None and np.array_equal(mine["above"][4: 4 + offs.size - 1], a3[1])
+assert np.array_equal(mine["below"][4: 4 + offs.size - 1], a3[2]) and (mine["above"][:4] == 77).all() and (mine["above"][3 + offs.size:] == 77).all()
 # the vectors as text: gap + "v v v \n" per read, offsets of every record
 gap = np.array([len("read_%d" % q) + 2 for q in range(offs.size - 1)], dtype=np.uint32)
 tx = ix.query_text(capi.SPX_MODE_MS, seqs, offs, gap=gap, streams=1 | 2 | 4, classify=(60, 6))
