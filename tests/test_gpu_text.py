@@ -6,26 +6,11 @@ import pytest
 
 from spumoni_amd import capi, synth
 from tests import cases
+from tests.text_lines import _expect, _fill
 
 pytestmark = pytest.mark.gpu
 
 DNA = list(b"ACGT")
-
-
-def _expect(values, offs, ids):
-    out = bytearray()
-    for q, name in enumerate(ids):
-        out += b">" + name + b"\n"
-        out += b"".join(b"%d " % int(v) for v in values[offs[q]: offs[q + 1]]) + b"\n"
-    return bytes(out)
-
-
-def _fill(text, line_start, ids):
-    b = bytearray(text)
-    for q, name in enumerate(ids):
-        at = int(line_start[q])
-        b[at: at + len(name) + 2] = b">" + name + b"\n"
-    return bytes(b)
 
 
 @pytest.mark.parametrize("seed,letters", [(51, DNA + [ord("N")]), (52, [3, 4, 5, 90, 127, 128, 129, 200, 255])])
