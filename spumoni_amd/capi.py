@@ -572,6 +572,51 @@ class Index:
         _check(_spm().spm_last_mems_stats(self._h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SpmMemsStats._fields_}
 
+    # -- placements (include/spumoni_place.h) ---------------------------------------
+    def place_device(self, d_seqs, d_lengths, d_pointers, d_offs, min_seed, mismatch_penalty=4, x_drop=16, d_docs=None,
+                     d_out=None, total_values=None, stream=None):
+        """One record per read (spp_placement, place.PLACEMENT_DTYPE: where the read's longest match, extended without gaps,
+        sits on the text) from the reads, the MS lengths and pointers of a query and the text the index holds, on the device:
+        returns d_out, an int32 tensor of shape (reads, 8).  int16 / uint16 lengths select the 16-bit form (d_docs has the
+        same width).  total_values: d_offs[-1] - d_offs[0] or an upper bound (default: what d_lengths holds)."""
+        import torch
+
+        L = _spp()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_offs.numel() - 1
+        if d_docs is not None and d_lengths.element_size() != d_docs.element_size():
+            raise SpxError("d_lengths and d_docs must have the same width")
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 8), dtype=torch.int32, device=d_offs.device)
+        total = d_lengths.numel() if total_values is None else int(total_values)
+        _check(L.spp_place_device(self._h, _t_ptr(d_seqs), _t_ptr(d_lengths), d_lengths.element_size() * 8, _t_ptr(d_pointers),
+                                  _t_ptr(d_docs), _t_ptr(d_offs), nreads, total, int(min_seed), int(mismatch_penalty), int(x_drop),
+                                  _t_ptr(d_out), C.c_void_p(st.cuda_stream)))
+        return d_out
+
+    def place_host(self, seqs, offs, min_seed, mismatch_penalty=4, x_drop=16, digest=None, want_docs=False):
+        """spp_place_batch: reads in, (records place.PLACEMENT_DTYPE[reads], values uint64[reads]) out; values = the read's
+        positions after digestion.  digest: (kind, k, w) or None."""
+        from .place import PLACEMENT_DTYPE
+
+        L = _spp()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=PLACEMENT_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        _check(L.spp_place_batch(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_seed), int(mismatch_penalty),
+                                 int(x_drop), 1 if want_docs else 0, _np_ptr(rec), _np_ptr(vals)))
+        return rec[:nreads], vals[:nreads]
+
+    def place_stats(self) -> dict:
+        """Of the most recent place_device / place_host call: values, placed reads, the sums of seed_len and of left + right,
+        kernel time."""
+        s = SppPlaceStats()
+        _check(_spp().spp_last_place_stats(self._h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in SppPlaceStats._fields_}
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -677,6 +722,31 @@ def _spm() -> C.CDLL:
         L.spm_mems_fetch.argtypes = [vp, vp, vp]
         L.spm_last_mems_stats.argtypes = [vp, C.POINTER(SpmMemsStats)]
         _SPM_READY = True
+    return L
+
+
+# ---- the placements (include/spumoni_place.h) -----------------------------------------------------------------------
+PLACE_EXPORTS = ["spp_place_device", "spp_place_batch", "spp_last_place_stats"]
+_SPP_READY = False
+
+
+class SppPlaceStats(C.Structure):
+    _fields_ = [("values", C.c_uint64), ("placed", C.c_uint64), ("seed_values", C.c_uint64), ("extended_values", C.c_uint64),
+                ("kernel_ms", C.c_float)]
+
+
+def _spp() -> C.CDLL:
+    """The library with the spp_* argtypes set (on first use)."""
+    global _SPP_READY
+    L = lib()
+    if not hasattr(L, "spp_place_batch"):
+        raise SpxError(f"{LIB_PATH} has no placement kernels (spp_place_batch): there is no CPU fallback")
+    if not _SPP_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spp_place_device.argtypes = [vp, vp, vp, i32, vp, vp, vp, u64, u64, u64, u32, u64, vp, vp]
+        L.spp_place_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, u32, u64, i32, vp, vp]
+        L.spp_last_place_stats.argtypes = [vp, C.POINTER(SppPlaceStats)]
+        _SPP_READY = True
     return L
 
 

@@ -281,6 +281,17 @@ struct spx_index {
     uint64_t mems_capacity = 0, mems_ready_n = 0;
     uint64_t mems_acc[4] = {};  // values, matches, longest, error bits
     float mems_ms = 0;
+    // placements (spx_place.hip): the counters (under mu), then the two buffer sets of spp_place_batch's pipeline,
+    // PL_SET_STRIDE slots each (under host_mu; its streams are assign_s); the events around the placement kernels of
+    // the last call and what that call counted
+    enum { PL_COUNTERS, PL_SET0, PL_SET_STRIDE = 8, PL_COUNT = PL_SET0 + 2 * PL_SET_STRIDE };
+    Scratch place_scr[PL_COUNT];
+    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+    hipStream_t place_stream = nullptr;
+    bool have_place = false, place_pending = false;
+    uint64_t place_acc[4] = {};  // values, placed, seed values, extended values
+    uint64_t place_error = 0;
+    float place_ms = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -339,6 +350,8 @@ int init_runtime(spx_index* ix);
 void release_votes(spx_index* ix);
 // spx_mems.hip: the same for the matches
 void release_mems(spx_index* ix);
+// spx_place.hip: the same for the placements
+void release_place(spx_index* ix);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
 int build_fat(spx_index* ix);
 // spx_walk.hip: MS text against the index: text[samples_start[k]] must be the head of run k
