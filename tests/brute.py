@@ -1,4 +1,10 @@
-"""Brute-force ground truth for tiny texts (first principles, no oracle / product code)."""
+"""Brute-force ground truth (first principles, no oracle / product code): Python for tiny texts, tests/brute_index.c
+for the index of texts up to about 10^6 characters."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
 import numpy as np
 
 
@@ -63,6 +69,102 @@ def select_brute(bwt, i, c):
                 return p
             cnt += 1
     raise IndexError
+
+
+# ---------------------------------------------------------------------------------------------
+# the index of a text (include/spumoni_build.h, synth.index_from_text) from first principles
+INDEX_FIELDS = ("heads", "lens", "thr", "ssa", "esa", "doc_start", "doc_end")
+
+
+def _brute_spec(text, doc_lengths):
+    """The specification restated over naive_sa / naive_lcp: for texts of a few hundred characters."""
+    t = list(text) + [0]
+    n = len(t)
+    sa = naive_sa(t)
+    lcp = naive_lcp(t, sa)
+    bwt = [t[(s - 1) % n] for s in sa]
+    starts = [i for i in range(n) if i == 0 or bwt[i] != bwt[i - 1]]
+    ends = [s - 1 for s in starts[1:]] + [n - 1]
+    heads = [bwt[s] for s in starts]
+    thr, last_end = [], {}
+    for k, c in enumerate(heads):
+        if c in last_end:
+            lo, hi = last_end[c] + 1, starts[k]
+            thr.append(min(range(lo, hi + 1), key=lambda i: (lcp[i], i)))
+        else:
+            thr.append(0)
+        last_end[c] = ends[k]
+    ssa = [(sa[s] - 1) % n for s in starts]
+    esa = [(sa[e] - 1) % n for e in ends]
+    cum = np.cumsum(doc_lengths)
+    cum[-1] += 1
+    ds = np.searchsorted(cum, ssa, side="right")
+    de = np.searchsorted(cum, esa, side="right")
+    return dict(heads=heads, lens=[e - s + 1 for s, e in zip(starts, ends)], thr=thr, ssa=ssa, esa=esa,
+                doc_start=ds.tolist(), doc_end=de.tolist())
+
+
+BRUTE_INDEX_C = os.path.join(os.path.dirname(os.path.abspath(__file__)), "brute_index.c")
+_brute_index_lib = None  # (the ctypes library, the temporary directory that holds it)
+
+
+def _index_lib():
+    """tests/brute_index.c compiled with gcc into a temporary directory, once per process."""
+    global _brute_index_lib
+    if _brute_index_lib is None:
+        d = tempfile.TemporaryDirectory(prefix="brute_index_")
+        so = os.path.join(d.name, "libbrute_index.so")
+        subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", so, BRUTE_INDEX_C], check=True)
+        L = C.CDLL(so)
+        vp = C.c_void_p
+        L.brute_index.restype = C.c_int
+        L.brute_index.argtypes = [vp, C.c_uint64, vp, C.c_uint32] + [vp] * 10
+        _brute_index_lib = (L, d)
+    return _brute_index_lib[0]
+
+
+class BruteIndex:
+    """What brute_index.c computed: n, r, sa and lcp (n entries each) and the seven fields (r entries each; the
+    document ids are None without doc_lengths, samples and ids are None where `with_samples` was false)."""
+
+    def __init__(self, text, doc_lengths=None, with_samples=True):
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        n = text.size + 1
+        dl = None if doc_lengths is None else np.ascontiguousarray(np.asarray(list(doc_lengths), dtype=np.uint64))
+        self.n = n
+        self.sa, self.lcp = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        heads = np.empty(n, dtype=np.uint8)
+        six = [np.zeros(n, dtype=np.uint64) for _ in range(6)]
+        r = C.c_uint64(0)
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        rc = _index_lib().brute_index(ptr(text), text.size, ptr(dl), 0 if dl is None else dl.size, ptr(self.sa), ptr(self.lcp),
+                                      C.addressof(r), ptr(heads), *[ptr(a) for a in six])
+        if rc != 0:
+            raise ValueError("brute_index refused the text (empty, a byte below 2, or document lengths that do not sum to it)")
+        self.r = r = int(r.value)
+        lens, thr, ssa, esa, ds, de = (a[:r].astype(np.int64) for a in six)
+        self.heads, self.lens, self.thr = heads[:r].copy(), lens, thr
+        self.ssa, self.esa = (ssa, esa) if with_samples else (None, None)
+        self.doc_start, self.doc_end = (ds, de) if with_samples and dl is not None else (None, None)
+
+    def mismatches(self, got):
+        """Names of the fields in which `got` (a synth.RawIndex, or anything with these attributes as tensors or
+        arrays) differs from this answer; ["n"] if the sizes differ."""
+        if int(got.n) != self.n:
+            return ["n"]
+        bad = []
+        for f in INDEX_FIELDS:
+            a, b = getattr(got, f), getattr(self, f)
+            if (a is None) != (b is None):
+                bad.append(f)
+            elif a is not None:
+                a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+                if a.shape != b.shape or not np.array_equal(a.astype(np.int64), b.astype(np.int64)):
+                    bad.append(f)
+        return bad
 
 
 # ---------------------------------------------------------------------------------------------

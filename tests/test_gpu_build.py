@@ -1,6 +1,6 @@
 """The HIP index builder (include/spumoni_build.h) on the device: every field bit-identical to the
-specification synth.index_from_text, brute force on small texts, a build past 2^31 characters, build_index through it,
-and its refusals."""
+specification synth.index_from_text, brute force on small texts, the catalogue of tests/build_cases.py against the
+first-principles reference tests/brute_index.c, a build past 2^31 characters, build_index through it, and its refusals."""
 import os
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from spumoni_amd import build_index, capi, synth
-from tests import brute, cases
+from tests import brute, build_cases, cases
 
 pytestmark = pytest.mark.gpu
 
@@ -34,37 +34,9 @@ def _check(text, doc_lengths=None, with_samples=True, spec_device="cuda"):
     return got
 
 
-def _brute_spec(text, doc_lengths):
-    """The specification restated over the naive suffix array / LCP of tests/brute.py."""
-    t = list(text) + [0]
-    n = len(t)
-    sa = brute.naive_sa(t)
-    lcp = brute.naive_lcp(t, sa)
-    bwt = [t[(s - 1) % n] for s in sa]
-    starts = [i for i in range(n) if i == 0 or bwt[i] != bwt[i - 1]]
-    ends = [s - 1 for s in starts[1:]] + [n - 1]
-    heads = [bwt[s] for s in starts]
-    thr, last_end = [], {}
-    for k, c in enumerate(heads):
-        if c in last_end:
-            lo, hi = last_end[c] + 1, starts[k]
-            thr.append(min(range(lo, hi + 1), key=lambda i: (lcp[i], i)))
-        else:
-            thr.append(0)
-        last_end[c] = ends[k]
-    ssa = [(sa[s] - 1) % n for s in starts]
-    esa = [(sa[e] - 1) % n for e in ends]
-    cum = np.cumsum(doc_lengths)
-    cum[-1] += 1
-    ds = np.searchsorted(cum, ssa, side="right")
-    de = np.searchsorted(cum, esa, side="right")
-    return dict(heads=heads, lens=[e - s + 1 for s, e in zip(starts, ends)], thr=thr, ssa=ssa, esa=esa,
-                doc_start=ds.tolist(), doc_end=de.tolist())
-
-
 def _check_brute(text, doc_lengths):
     got = capi.build_raw(np.asarray(text, dtype=np.uint8), doc_lengths=doc_lengths)
-    want = _brute_spec(text, doc_lengths)
+    want = brute._brute_spec(text, doc_lengths)
     assert got.n == len(text) + 1
     for f, v in want.items():
         assert getattr(got, f).tolist() == v, (bytes(text), doc_lengths, f)
@@ -87,6 +59,26 @@ def test_brute_force_random_texts(sigma):
         cuts = sorted(set(rng.integers(1, length, size=min(3, length - 1)).tolist())) if length > 1 else []
         docs = np.diff([0] + cuts + [length]).tolist()
         _check_brute(text, docs)
+
+
+def _check_case(case):
+    """capi.build_raw against the C reference alone, after the reference shows that the case reaches its path."""
+    text, docs, samples, ref = build_cases.reference(case)
+    assert not case.unmet(ref), "the case does not reach what it is for"
+    got = capi.build_raw(text, doc_lengths=docs, with_samples=samples)
+    assert ref.mismatches(got) == []
+    assert np.array_equal(got.text.numpy(), text)
+
+
+@pytest.mark.parametrize("case", build_cases.CASES, ids=lambda c: c.name)
+def test_catalogue_against_first_principles(case):
+    _check_case(case)
+
+
+def test_largest_case_directly_after_the_smallest():
+    """One process, no other build in between: nothing of a build of 62 characters may be left for one of 2^20."""
+    for case in (build_cases.SMALLEST, build_cases.LARGEST, build_cases.SMALLEST):
+        _check_case(case)
 
 
 @pytest.mark.parametrize("kind", ["one_letter", "alternating", "byte_255", "single"])
@@ -238,6 +230,14 @@ def test_build_index_files_identical_to_the_torch_path(tmp_path, monkeypatch):
 
 def _still_works():
     _check(np.frombuffer(b"GATTACAGATTACACATTAG", dtype=np.uint8), doc_lengths=[7, 13])
+
+
+def test_one_document_past_the_limit_is_refused_by_name():
+    """65 535 documents are built (build_cases.py: documents_65535); 65 536 are not."""
+    text = np.full(70_000, 65, dtype=np.uint8)
+    with pytest.raises(capi.SpxError, match="65536 documents: the builder takes 1 to 65535"):
+        capi.build_raw(text, doc_lengths=[1] * 65_535 + [70_000 - 65_535])
+    _check_case(build_cases.SMALLEST)
 
 
 def test_refusals_leave_the_device_usable():
