@@ -168,6 +168,46 @@ class BruteIndex:
 
 
 # ---------------------------------------------------------------------------------------------
+# matching statistics of a batch of reads from first principles (tests/brute_ms.c: binary search over `sa`)
+BRUTE_MS_C = os.path.join(os.path.dirname(os.path.abspath(__file__)), "brute_ms.c")
+_brute_ms_lib = None
+
+
+def _ms_lib():
+    """tests/brute_ms.c compiled with gcc into a temporary directory, once per process."""
+    global _brute_ms_lib
+    if _brute_ms_lib is None:
+        d = tempfile.TemporaryDirectory(prefix="brute_ms_")
+        so = os.path.join(d.name, "libbrute_ms.so")
+        subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", so, BRUTE_MS_C], check=True)
+        L = C.CDLL(so)
+        vp = C.c_void_p
+        L.brute_ms.restype = C.c_int
+        L.brute_ms.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
+        _brute_ms_lib = (L, d)
+    return _brute_ms_lib[0]
+
+
+def brute_ms(text, sa, seqs, offs):
+    """The matching statistic of every position of every read (uint32, offs[-1] values): the longest prefix of
+    read[i:] that occurs in `text`.  sa: the suffix array of text + terminator (BruteIndex.sa)."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    if sa.size != text.size + 1 or offs.size < 1 or int(offs[-1]) > seqs.size:
+        raise ValueError("brute_ms: sa has n_text + 1 entries, offs ends inside seqs")
+    tot = int(offs[-1])
+    out = np.zeros(max(tot, 1), dtype=np.uint32)
+    pad = np.concatenate([seqs, np.zeros(1, dtype=np.uint8)])  # (a valid address for an empty batch)
+    rc = _ms_lib().brute_ms(text.ctypes.data, text.size, sa.ctypes.data, pad.ctypes.data, offs.ctypes.data, offs.size - 1,
+                            out.ctypes.data)
+    if rc != 0:
+        raise ValueError("brute_ms refused its input (sa is no permutation, or offsets that fall)")
+    return out[:tot]
+
+
+# ---------------------------------------------------------------------------------------------
 # minimizer digestion, written as a specification (slices and min(), no queue): what
 # oracle/orc_digest.c and the HIP kernel must both produce.  See DESIGN.md 4.4 for the
 # assumptions about bonsai this encodes.

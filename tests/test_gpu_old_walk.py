@@ -9,7 +9,8 @@ round 3, so the ordinary run walks it with k_walk_fast as well; it was left out 
 numpy loop: profiles/r03_slow_test_probe.txt).  tests/test_gpu_field_widths.py runs here too: k_walk_lanes over the compact
 rows and pieces of an index of 2^40 - 3 positions; and tests/test_gpu_classify.py: its fused classifier over the compact rows,
 over every bin width and threshold; and tests/test_gpu_used_handle.py: this walk is the only kernel that writes the reset-bit
-scratch (C_LEN_BITS), which that module reuses across calls of different sizes on one handle."""
+scratch (C_LEN_BITS), which that module reuses across calls of different sizes on one handle; and tests/test_gpu_ms_math.py:
+this walk held to matching statistics from first principles on the same cases as k_walk_fast."""
 import os
 import subprocess
 import sys
@@ -30,7 +31,7 @@ def test_parity_suite_on_the_state_machine_walk():
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
                         "tests/test_gpu_parity.py", "tests/test_golden.py",
                         "tests/test_gpu_fuzz.py", "tests/test_gpu_field_widths.py", "tests/test_gpu_classify.py",
-                        "tests/test_gpu_used_handle.py", "-k", "not scale"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1700)
+                        "tests/test_gpu_used_handle.py", "tests/test_gpu_ms_math.py", "-k", "not scale"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1700)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
     assert " passed" in p.stdout
 
