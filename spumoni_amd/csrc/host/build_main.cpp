@@ -29,6 +29,7 @@
 #include "../../../include/spumoni_build.h"
 #include "../../../include/spumoni_gpu.h"
 #include "../../../include/spumoni_reftext.h"
+#include "read_command.hpp"
 #include "reads.hpp"
 
 using namespace spumoni_host;
@@ -55,16 +56,9 @@ namespace {
 
 constexpr size_t NULL_READ_CHUNK = 150, NUM_NULL_READS = 800, NULL_READ_BOUND = 1000;  // spumoni_main.hpp:65-67
 
-bool is_file(const std::string& p) {
-    struct stat st;
-    return ::stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
 bool is_dir(const std::string& p) {
     struct stat st;
     return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-bool ends_with(const std::string& s, const std::string& suf) {
-    return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;
 }
 bool fasta_name(const std::string& p) {  // the reference's extensions, gzip-compressed or not
     const std::string q = ends_with(p, ".gz") ? p.substr(0, p.size() - 3) : p;

@@ -1,0 +1,239 @@
+// read_command.cpp -- the driver under `spumoni assign`, `mems` and `place` (read_command.hpp).
+#include "read_command.hpp"
+
+#include <dlfcn.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+
+#include "index_files.hpp"
+
+namespace spumoni_host {
+
+bool is_file(const std::string& path) {
+    struct stat st;
+    return ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+bool ends_with(const std::string& s, const std::string& suffix) {
+    return s.size() >= suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0;
+}
+
+void pin_charhash(const std::vector<spx_index*>& handles) {
+    const char* pin = std::getenv("SPUMONI_CHARHASH");
+    if (!pin) return;
+    unsigned v[4] = {0, 0, 0, 0};
+    if (std::sscanf(pin, "%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3]) != 4)
+        fatal_error("SPUMONI_CHARHASH must be four comma-separated byte values (A,C,G,T)");
+    const int64_t packed = (int64_t)((v[0] & 255) | ((v[1] & 255) << 8) | ((v[2] & 255) << 16) | ((uint64_t)(v[3] & 255) << 24));
+    for (spx_index* ix : handles)
+        if (spx_set_option(ix, "minimizer_charhash", packed) != SPX_OK) fatal_error("%s", spx_last_error());
+}
+
+void parse_read_options(int argc, char** argv, ReadOptions& o, int (*usage)(), bool doc_option, const char* extra_short,
+                        const std::vector<struct option>& extra_long, const std::function<void(int, const char*)>& extra) {
+    std::vector<struct option> table = {{"help", no_argument, NULL, 'h'},
+                                        {"ref", required_argument, NULL, 'r'},
+                                        {"pattern", required_argument, NULL, 'p'},
+                                        {"MS", no_argument, NULL, 'M'},
+                                        {"PML", no_argument, NULL, 'P'},
+                                        {"no-digest", no_argument, NULL, 'n'},
+                                        {"minimizer-alphabet", no_argument, NULL, 'm'},
+                                        {"dna-minimizer", no_argument, NULL, 'a'},
+                                        {"small-window", required_argument, NULL, 'K'},
+                                        {"large-window", required_argument, NULL, 'W'}};
+    std::string shorts = "hr:p:MPnmaK:W:";
+    if (doc_option) {
+        table.push_back({"doc-array", no_argument, NULL, 'd'});
+        shorts += "d";
+    }
+    table.insert(table.end(), extra_long.begin(), extra_long.end());
+    shorts += extra_short;
+    table.push_back({0, 0, 0, 0});
+    int long_index = 0;
+    for (int c; (c = getopt_long(argc, argv, shorts.c_str(), table.data(), &long_index)) >= 0;) {
+        switch (c) {
+            case 'r': o.ref_file.assign(optarg); break;
+            case 'p': o.pattern_file.assign(optarg); break;
+            case 'M': o.ms_requested = true; break;
+            case 'P': o.pml_requested = true; break;
+            case 'm': o.use_promotions = true; break;
+            case 'a': o.use_dna_letters = true; break;
+            case 'n': o.min_digest = false; break;
+            case 'K': o.k = std::max(std::atoi(optarg), 1); break;
+            case 'W': o.w = std::max(std::atoi(optarg), 1); break;
+            case 'd': o.use_doc = true; break;
+            case 'h':
+            case '?':
+            case ':': usage(); std::exit(1);
+            default: extra(c, optarg);
+        }
+    }
+}
+
+void require_ref_and_pattern(const ReadOptions& o) {
+    if (o.ref_file == "" || o.pattern_file == "") fatal_warning("Both a reference file (-r) and pattern file (-p) must be provided.");
+}
+
+void validate_read_options(const ReadOptions& o) {
+    const std::string base = o.ref_file + (o.use_promotions ? ".bin" : ".fa");
+    if (!is_file(base)) fatal_error("The following path is not valid: %s (remember to only specify output prefix)", base.data());
+    if (!is_file(o.pattern_file)) fatal_error("The following path is not valid: %s", o.pattern_file.data());
+    if (!ends_with(o.pattern_file, ".fa") && !ends_with(o.pattern_file, ".fasta") && !ends_with(o.pattern_file, ".fna"))
+        fatal_error("The pattern file provided does not appear to be a FASTA\n"
+                    "       file, please convert to FASTA and re-run.");
+    if (o.use_doc && !is_file(base + ".doc"))
+        fatal_warning("document array file (%s) is not present, so it cannot be used.", (base + ".doc").data());
+    const bool have_raw = is_file(base + ".bwt.heads") && is_file(base + ".bwt.len") && is_file(base + ".thr_pos") &&
+                          (!o.ms || (is_file(base + ".ssa") && is_file(base + ".esa")));
+    if (!have_raw && !is_file(base + (o.ms ? ".thrbv.ms" : ".thrbv.spumoni")))
+        fatal_warning("The index required for this computation is not available, please use spumoni build.");
+    if (o.k > 4) fatal_warning("small window size (k) cannot be larger than 4 characters.");
+    if (o.w < o.k) fatal_warning("large window size (w) should be larger than the small window size (k)");
+    if (o.min_digest) {
+        if (o.use_promotions && o.use_dna_letters) fatal_error("Only one type of minimizer can be specified from either -m or -a.");
+        if (!o.use_promotions && !o.use_dna_letters) fatal_error("A minimizer type must be specified using -m or -a.");
+    } else if (o.use_promotions || o.use_dna_letters) {
+        fatal_error("A minimizer type should not be specified if intending not to use minimizer digestion.");
+    }
+}
+
+std::vector<void*> device_entry_points(const char* command, const std::vector<const char*>& names, const char* what) {
+    std::vector<void*> found;
+    for (const char* name : names) found.push_back(dlsym(RTLD_DEFAULT, name));
+    if (std::find(found.begin(), found.end(), nullptr) != found.end())
+        fatal_error("the loaded libspumoni_gpu.so has no %s: `spumoni %s` needs %s of "
+                    "the device library, and there is no CPU fallback.", names[0], command, what);
+    if (spx_device_count() <= 0) fatal_error("no usable gfx950 device: `spumoni %s` runs on the GPU and has no CPU fallback.", command);
+    return found;
+}
+
+void open_read_run(ReadOptions& o, size_t default_super_batch, ReadRun& run) {
+    int device = 0;
+    if (const char* g = std::getenv("SPUMONI_GPUS")) device = std::atoi(g);
+    if (const char* t = std::getenv("SPUMONI_TEXT")) o.text_file = t;
+    run.super_batch = default_super_batch;
+    if (const char* t = std::getenv("SPUMONI_SUPER_BATCH")) run.super_batch = std::max<size_t>(1000, std::strtoull(t, nullptr, 10));
+    run.t_start = std::chrono::steady_clock::now();
+    try {
+        run.reads.reset(new ReadFile(o.pattern_file));
+    } catch (const std::exception& e) {
+        fatal_error("%s", e.what());
+    }
+    {
+        RunOptions lo = o;
+        lo.devices = {device};
+        lo.pattern_file.clear();  // (nothing of `run`'s text output is reserved)
+        run.set.load(lo);
+    }
+    run.ix = run.set.ix[0];
+    if (o.use_promotions) pin_charhash({run.ix});
+    run.digest_kind = o.use_promotions ? SPX_DIGEST_PROMOTED : (o.use_dna_letters ? SPX_DIGEST_DNA : 0);
+}
+
+uint64_t null_db_threshold(const ReadOptions& o) {
+    double percentile = 0.0;
+    std::string err;
+    (void)load_null_db(o.ref_file + (o.ms ? ".msnulldb" : ".pmlnulldb"), percentile, err);
+    return max_value_threshold(percentile, !o.ms, o.use_promotions, o.use_dna_letters);
+}
+
+namespace {
+std::string g_partial;
+void drop_partial() {
+    if (!g_partial.empty()) ::unlink(g_partial.c_str());
+    g_partial.clear();
+}
+}  // namespace
+
+void LinesFile::open(const std::string& p, bool keep_partial_file) {
+    path = p;
+    keep_partial = keep_partial_file;
+    if (!keep_partial) set_exit_hook(drop_partial);
+    f = std::fopen(p.c_str(), "wb");
+    if (!f) fatal_error("cannot create %s", p.c_str());
+    if (!keep_partial) g_partial = p;
+    std::setvbuf(f, nullptr, _IOFBF, 1 << 20);
+}
+void LinesFile::close() {
+    if (f && std::fclose(f) != 0) fatal_error("write failed (disk full?): %s", path.c_str());
+    f = nullptr;
+    if (!keep_partial) g_partial.clear();
+}
+
+void scan_reads(ReadRun& run, LinesFile& out, const std::function<void(ReadBatch&)>& query,
+                const std::function<void(const ReadBatch&, size_t)>& line) {
+    ReadFile& reads = *run.reads;
+    ReadBatch b;
+    // 0 none, 1 a malformed record, 2 a read that is empty: fatal, as in `run`
+    int deferred = 0;
+    std::string deferred_msg;
+    auto flush = [&](size_t take) {
+        if (!take) return;
+        b.take = take;
+        b.offs.assign(1, 0);
+        size_t chars = 0;
+        for (size_t i = 0; i < take; ++i) b.offs.push_back(chars += b.recs[i].seq_len);
+        b.seqs.resize(chars + 1);
+        for (size_t i = 0; i < take; ++i) reads.copy_seq_upper(b.recs[i], b.seqs.data() + b.offs[i]);
+        b.values.resize(take + 1);
+        query(b);
+        for (size_t i = 0; i < take; ++i) {
+            if (b.values[i] == 0) {  // compute_ms_pml.cpp:926-931
+                deferred = 2;
+                deferred_msg.assign(b.recs[i].id, b.recs[i].id_len);
+                return;
+            }
+            line(b, i);
+        }
+    };
+    reads.precompute_ranges(1000);
+    ReadFile::Range range;
+    size_t pending_chars = 0;
+    while (!deferred && reads.next_range(1000, range)) {
+        ReadFile::ParseError err;
+        const size_t before = b.recs.size();
+        reads.scan_range(range, b.recs, err);
+        size_t take = b.recs.size();
+        for (size_t i = before; i < b.recs.size(); ++i) {
+            if (b.recs[i].seq_len == 0) {
+                deferred = 2;
+                deferred_msg.assign(b.recs[i].id, b.recs[i].id_len);
+                take = i;
+                break;
+            }
+            pending_chars += b.recs[i].seq_len;
+        }
+        if (!deferred && err.fatal) {
+            deferred = 1;
+            deferred_msg = err.message;
+        }
+        if (deferred && !out.keep_partial) break;
+        if (deferred || pending_chars >= run.super_batch) {  // (what is in front of the failing read is written first)
+            const int d = deferred;
+            const std::string msg = deferred_msg;
+            deferred = 0;
+            flush(take);
+            if (!deferred) {
+                deferred = d;
+                deferred_msg = msg;
+            }
+            b.recs.clear();
+            pending_chars = 0;
+        }
+    }
+    if (!deferred) flush(b.recs.size());
+    if (!deferred || out.keep_partial) out.close();
+    if (deferred == 1) fatal_error("%s", deferred_msg.c_str());
+    if (deferred == 2) {
+        std::cout << "\n\n";
+        fatal_warning("%s was empty after digestion, commonly due to reads "
+                      "consisting of mostly non-ACGT characters. Please remove "
+                      "read or run SPUMONI without minimizer digestion.", deferred_msg.data());
+    }
+}
+
+}  // namespace spumoni_host

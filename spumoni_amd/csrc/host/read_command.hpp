@@ -1,0 +1,80 @@
+// read_command.hpp -- what `spumoni assign`, `mems` and `place` share: a command that walks the reads of a FASTA / FASTQ
+// file through one product of the device library and writes lines in input order.  The shared options and their rules
+// (`run`'s messages where the rule is the same, spumoni_main.cpp: validate), the look-up of the product's entry points,
+// the run's set-up -- one device (the first of SPUMONI_GPUS), the reads from reads.cpp, the index through the loaders `run`
+// uses --, the loop over super-batches of SPUMONI_SUPER_BATCH characters, and the output file.  A command keeps its usage
+// text, its own options and checks, its call into the library, its lines and its closing line on stderr.
+#pragma once
+#include <getopt.h>
+
+#include <chrono>
+#include <cstdio>
+#include <functional>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "classify.hpp"
+#include "reads.hpp"
+
+namespace spumoni_host {
+
+bool is_file(const std::string& path);
+bool ends_with(const std::string& s, const std::string& suffix);
+// SPUMONI_CHARHASH=<A>,<C>,<G>,<T>: pins the 8-bit character hashes of the -m digestion on every handle (nothing without it)
+void pin_charhash(const std::vector<spx_index*>& handles);
+
+struct ReadOptions : RunOptions {
+    bool ms_requested = false, pml_requested = false;
+    bool have_threshold = false;  // the command's own -T / -L
+    uint64_t threshold = 0;
+};
+
+// -h -r -p -M -P -n -m -a -K -W [-d] and the command's own: `extra` gets every other option of extra_short / extra_long;
+// an unknown one prints the usage and ends the process with status 1
+void parse_read_options(int argc, char** argv, ReadOptions& o, int (*usage)(), bool doc_option, const char* extra_short,
+                        const std::vector<struct option>& extra_long, const std::function<void(int, const char*)>& extra);
+// the rules that do not depend on the command, in two parts: a command's own -M / -P rule stands between them and sets o.ms
+void require_ref_and_pattern(const ReadOptions& o);
+void validate_read_options(const ReadOptions& o);  // the paths, .doc with o.use_doc, the index files by o.ms, k, w, -m / -a
+// The command's entry points, looked up at run time and never linked: the binary must also load against libraries without
+// them (a CPU test double of the query boundary).  `what`: "the document votes".  Ends the process when one is missing or
+// no device is usable -- before any file is written.
+std::vector<void*> device_entry_points(const char* command, const std::vector<const char*>& names, const char* what);
+
+struct ReadRun {
+    std::chrono::steady_clock::time_point t_start;
+    std::unique_ptr<ReadFile> reads;
+    IndexSet set;
+    spx_index* ix = nullptr;
+    size_t super_batch = 0;
+    int digest_kind = 0;
+};
+// o.ref_file with its extension, o.ms set.  SPUMONI_GPUS, SPUMONI_TEXT, SPUMONI_SUPER_BATCH, SPUMONI_CHARHASH.
+void open_read_run(ReadOptions& o, size_t default_super_batch, ReadRun& run);
+// the default of -T / -L: what `run -c` classifies with, from the null database (classify.cpp)
+uint64_t null_db_threshold(const ReadOptions& o);
+
+// Lines in input order, plain buffered writes.  keep_partial false: a run that fails leaves no file (every way out through
+// fatal_error / fatal_warning unlinks it).
+struct LinesFile {
+    std::string path;
+    FILE* f = nullptr;
+    bool keep_partial = true;
+    void open(const std::string& p, bool keep_partial_file);
+    void close();
+};
+
+struct ReadBatch {
+    std::vector<ReadRec> recs;  // the first `take` are the batch
+    size_t take = 0;
+    std::vector<uint8_t> seqs;
+    std::vector<uint64_t> offs, values;  // values: per read, what the library says it had after digestion
+};
+// Scans the reads; per super-batch `query` calls the library (it fills values) and `line` writes read i's lines.  A
+// malformed record or a read that is empty (before or after digestion) is fatal as in `run`: with out.keep_partial the
+// reads in front of it are flushed and the file is closed first, else nothing more is flushed.  Closes `out`.
+void scan_reads(ReadRun& run, LinesFile& out, const std::function<void(ReadBatch&)>& query,
+                const std::function<void(const ReadBatch&, size_t)>& line);
+
+}  // namespace spumoni_host

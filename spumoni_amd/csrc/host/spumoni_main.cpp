@@ -26,6 +26,7 @@
 
 #include "classify.hpp"
 #include "index_files.hpp"
+#include "read_command.hpp"
 #include "reads.hpp"
 
 #define SPUMONI_VERSION "2.0.9"  // include/spumoni_main.hpp:24 (the version this build mirrors)
@@ -49,14 +50,6 @@ using namespace spumoni_host;
         auto sec = std::chrono::duration<double>(x);              \
         std::fprintf(stderr, "done.  (%.3f sec)\n", sec.count()); \
     } while (0)
-
-static int is_file(const std::string& path) {
-    struct stat st;
-    return ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
-static bool ends_with(const std::string& s, const std::string& suf) {
-    return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;
-}
 
 static int spumoni_run_usage() {
     std::fprintf(stderr, "spumoni run - Uses a spumoni index to compute MS/PML of patterns w.r.t. a reference.\n");
@@ -260,14 +253,7 @@ static int run_spumoni(CliOptions& o) {  // run_spumoni_main / run_spumoni_ms_ma
                      o.use_promotions ? (pin ? "  Character hashes pinned by SPUMONI_CHARHASH."
                                              : "  Pin the -m character hashes with SPUMONI_CHARHASH=<A>,<C>,<G>,<T>.")
                                       : "");
-        if (pin && o.use_promotions) {
-            unsigned v[4] = {0, 0, 0, 0};
-            if (std::sscanf(pin, "%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3]) != 4)
-                fatal_error("SPUMONI_CHARHASH must be four comma-separated byte values (A,C,G,T)");
-            const int64_t packed = (int64_t)((v[0] & 255) | ((v[1] & 255) << 8) | ((v[2] & 255) << 16) | ((uint64_t)(v[3] & 255) << 24));
-            for (spx_index* p : set.ix)
-                if (spx_set_option(p, "minimizer_charhash", packed) != SPX_OK) fatal_error("%s", spx_last_error());
-        }
+        if (o.use_promotions) pin_charhash(set.ix);
     }
     start_time = std::chrono::system_clock::now();
     STATUS_LOG(tag, o.ms ? "processing the reads" : "processing the patterns");

@@ -175,6 +175,7 @@ void spx_index_free(spx_index* ix) {
         if (sc.p) (void)hipFree(sc.p);
     for (auto& sc : ix->digest_scr)
         if (sc.p) (void)hipFree(sc.p);
+    release_stage(ix);
     release_votes(ix);
     release_mems(ix);
     release_place(ix);

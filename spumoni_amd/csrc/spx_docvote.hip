@@ -41,6 +41,7 @@ struct VoteCounters {  // device; zeroed in front of every launch
     unsigned long long n_medium, n_long, n_tiles, table_used;  // fill of the lists; values the long reads' tables are for
     unsigned long long error;  // bit 0: a read of 2^32 values or more; bit 1: the batch holds more than total_values said
 };
+constexpr int VOTE_WORDS = sizeof(VoteCounters) / 8;  // (the first six are what spv_votes_stats reports, the last the error)
 struct LongAcc {  // 32 B per long read
     unsigned long long top;  // max of (count << 32 | ~id)
     unsigned int voters, second;
@@ -389,10 +390,6 @@ int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int 
                   hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    if (!ix->ev_v0) {
-        SPX_HIP(hipEventCreate(&ix->ev_v0));
-        SPX_HIP(hipEventCreate(&ix->ev_v1));
-    }
     VoteArgs a{};
     a.L = (const uint4*)d_lengths;
     a.D = (const uint4*)d_docs;
@@ -407,8 +404,6 @@ int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int 
     a.table_cap = a.long_cap ? std::min(long_values, total_values) : 0;
     void* p = nullptr;
     int rc;
-    if ((rc = ix->vote_scr[spx_index::V_COUNTERS].reserve(sizeof(VoteCounters), &p)) != SPX_OK) return rc;
-    a.c = (VoteCounters*)p;
     if ((rc = ix->vote_scr[spx_index::V_MEDIUM].reserve(a.medium_cap * 8, &p)) != SPX_OK) return rc;
     a.medium_list = (uint64_t*)p;
     if ((rc = ix->vote_scr[spx_index::V_LONG].reserve(a.long_cap * 8, &p)) != SPX_OK) return rc;
@@ -419,11 +414,9 @@ int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int 
     a.acc = (LongAcc*)p;
     if ((rc = ix->vote_scr[spx_index::V_TABLE].reserve(a.table_cap * 16, &p)) != SPX_OK) return rc;
     a.table = (uint4*)p;
-    // the counters, lists and events are the index's: a call on another stream waits for the one before
-    if (ix->have_votes && ix->vote_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_v1, 0));
-    SPX_HIP(hipMemsetAsync(a.c, 0, sizeof(VoteCounters), st));
-    SPX_HIP(hipEventRecord(ix->ev_v0, st));
-    if (nreads) {
+    return product_enqueue(ix->votes, VOTE_WORDS, st, [&](void* counters) -> int {
+        a.c = (VoteCounters*)counters;
+        if (!nreads) return SPX_OK;
         const unsigned short_grid = (unsigned)std::min<uint64_t>((nreads + 15) / 16, 2048);
         const unsigned medium_grid = (unsigned)std::min<uint64_t>(a.medium_cap, 1280);
         if (value_bits == 16) {
@@ -445,41 +438,15 @@ int votes_enqueue(spx_index* ix, const void* d_lengths, const void* d_docs, int 
             k_long_write<<<(unsigned)std::min<uint64_t>((a.long_cap + 255) / 256, 64), 256, 0, st>>>(a);
         }
         SPX_HIP(hipGetLastError());
-    }
-    SPX_HIP(hipEventRecord(ix->ev_v1, st));
-    ix->have_votes = true;
-    ix->vote_stream = st;
-    return SPX_OK;
-}
-
-// Waits for the vote kernels enqueued last and adds what they counted to ix->vote_acc / vote_ms.  Takes ix->mu.
-int votes_collect(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventSynchronize(ix->ev_v1));
-    VoteCounters c;
-    SPX_HIP(hipMemcpy(&c, ix->vote_scr[spx_index::V_COUNTERS].p, sizeof c, hipMemcpyDeviceToHost));
-    float ms = 0;
-    SPX_HIP(hipEventElapsedTime(&ms, ix->ev_v0, ix->ev_v1));
-    const unsigned long long v[6] = {c.reads_short, c.reads_medium, c.reads_long, c.reads_empty, c.voting, c.tiles};
-    for (int i = 0; i < 6; ++i) ix->vote_acc[i] += v[i];
-    ix->vote_ms += ms;
-    ix->vote_error |= c.error;
-    return SPX_OK;
-}
-void votes_reset(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->vote_acc, 0, sizeof ix->vote_acc);
-    ix->vote_ms = 0;
-    ix->vote_error = 0;
-    ix->vote_pending = false;
+        return SPX_OK;
+    });
 }
 int vote_error_code(const spx_index* ix) {
-    if (ix->vote_error & 1) {
+    if (ix->votes.error & 1) {
         set_error("a read has 2^32 values or more (or its offsets decrease): the votes take reads below that");
         return SPX_E_FORMAT;
     }
-    if (ix->vote_error & 2) {
+    if (ix->votes.error & 2) {
         set_error("the batch holds more values than total_values said: the records are undefined");
         return SPX_E_FORMAT;
     }
@@ -503,10 +470,7 @@ int check_index(const spx_index* ix) {
 void release_votes(spx_index* ix) {
     for (auto& sc : ix->vote_scr)
         if (sc.p) (void)hipFree(sc.p);
-    for (auto& st : ix->assign_s)
-        if (st) (void)hipStreamDestroy(st);
-    if (ix->ev_v0) (void)hipEventDestroy(ix->ev_v0);
-    if (ix->ev_v1) (void)hipEventDestroy(ix->ev_v1);
+    product_release(ix->votes);
 }
 
 }  // namespace spx
@@ -531,11 +495,9 @@ int spv_votes_device(spx_index* ix, const void* d_lengths, const void* d_docs, i
         set_error("d_lengths, d_docs and d_out must be 16-byte aligned (the values are read as 16-byte vectors)");
         return SPX_E_ARG;
     }
-    votes_reset(ix);
-    rc = votes_enqueue(ix, d_lengths, d_docs, value_bits, d_offsets, nreads, total_values, total_values, min_length, d_out,
-                       (hipStream_t)stream);
-    if (rc == SPX_OK) ix->vote_pending = true;
-    return rc;
+    product_reset(ix, ix->votes);
+    return votes_enqueue(ix, d_lengths, d_docs, value_bits, d_offsets, nreads, total_values, total_values, min_length, d_out,
+                         (hipStream_t)stream);
 }
 
 int spv_last_votes_stats(spx_index* ix, spv_votes_stats* out) {
@@ -543,28 +505,25 @@ int spv_last_votes_stats(spx_index* ix, spv_votes_stats* out) {
         set_error("null argument");
         return SPX_E_ARG;
     }
-    if (!ix->have_votes) {
+    if (!ix->votes.have) {
         set_error("no votes have been computed on this index yet");
         return SPX_E_ARG;
     }
-    if (ix->vote_pending) {
-        const int rc = votes_collect(ix);
+    if (ix->votes.pending) {
+        const int rc = product_collect(ix, ix->votes, VOTE_WORDS, 6);
         if (rc != SPX_OK) return rc;
-        ix->vote_pending = false;
     }
-    out->reads_short = ix->vote_acc[0];
-    out->reads_medium = ix->vote_acc[1];
-    out->reads_long = ix->vote_acc[2];
-    out->reads_empty = ix->vote_acc[3];
-    out->voting_positions = ix->vote_acc[4];
-    out->long_tiles = ix->vote_acc[5];
-    out->kernel_ms = ix->vote_ms;
+    out->reads_short = ix->votes.acc[0];
+    out->reads_medium = ix->votes.acc[1];
+    out->reads_long = ix->votes.acc[2];
+    out->reads_empty = ix->votes.acc[3];
+    out->voting_positions = ix->votes.acc[4];
+    out->long_tiles = ix->votes.acc[5];
+    out->kernel_ms = ix->votes.ms;
     return vote_error_code(ix);
 }
 
-// Pieces of about PIECE_CHARS characters alternate between two buffer sets and two streams: a piece's reads are copied
-// in while the piece before is digested, walked and voted on (queries on one index are serialised; the copies are not).
-// A piece is finished -- its walk's and votes' counters read -- before the kernels of the next are enqueued.
+// The staged walk (spx_stage.hip) with the vote kernels behind every piece's walk.
 int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs,
                      const uint64_t* offsets, uint64_t nreads, uint64_t min_length, spv_vote* out, uint64_t* out_values) {
     if (spx_device_count() <= 0) {
@@ -592,133 +551,45 @@ int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint3
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
-    votes_reset(ix);
+    product_reset(ix, ix->votes);
     if (nreads == 0) return SPX_OK;
-    // the pieces, the widest read and what the long reads hold (a digestion only shortens them)
-    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
-    std::vector<uint64_t> cut{0};
-    uint64_t longest = 0, worst_chars = 0, worst_reads = 0, worst_long = 0, piece_long = 0;
-    for (uint64_t q = 0; q < nreads; ++q) {
-        if (offsets[q + 1] < offsets[q]) {
-            set_error("offsets must not decrease (read %llu)", (unsigned long long)q);
-            return SPX_E_ARG;
-        }
-        const uint64_t m = offsets[q + 1] - offsets[q];
-        longest = std::max(longest, m);
-        if (m > MEDIUM_MAX) piece_long += m;
-        const uint64_t q0 = cut.back();
-        if (q + 1 == nreads || offsets[q + 1] - offsets[q0] >= PIECE_CHARS || q + 1 - q0 >= PIECE_READS) {
-            worst_chars = std::max(worst_chars, offsets[q + 1] - offsets[q0]);
-            worst_reads = std::max(worst_reads, q + 1 - q0);
-            worst_long = std::max(worst_long, piece_long);
-            piece_long = 0;
-            cut.push_back(q + 1);
-        }
-    }
-    if (longest >= (1ull << 32)) {
-        set_error("a read has 2^32 characters or more");
-        return SPX_E_ARG;
-    }
-    const bool narrow = longest < 65536;
-    const size_t width = narrow ? 2 : 4;
-    for (auto& st : ix->assign_s)
-        if (!st) SPX_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // both buffer sets, sized for the largest piece before anything is enqueued (growing one frees it: a device-wide wait)
-    const uint64_t raw_bytes = ((worst_chars + 15) & ~15ull) + 64;
-    const uint64_t dig_bytes = digest_kind ? spx_digest_capacity(digest_kind, k, worst_chars) + 32 : 0;
-    struct Set {
-        uint8_t *raw, *dig;
-        uint64_t *off, *dig_off, *ptr;
-        void *len, *doc;
-        spv_vote* out;
-        std::vector<uint64_t> h_off, h_dig_off;
-    } set[2];
-    for (int b = 0; b < 2 && (b == 0 || cut.size() > 2); ++b) {
-        constexpr int NSET = spx_index::V_SET_STRIDE;
-        const size_t sizes[NSET] = {raw_bytes, (worst_reads + 1) * 8, dig_bytes, digest_kind ? (worst_reads + 1) * 8 : 0,
-                                 (worst_chars + 16) * width, (worst_chars + 16) * width,
-                                 mode == SPX_MODE_MS ? (worst_chars + 2) * 8 : 0, (worst_reads + 1) * sizeof(spv_vote)};
-        void* p[NSET] = {};
-        for (int i = 0; i < NSET; ++i)
-            if (sizes[i] && (rc = ix->vote_scr[spx_index::V_SET0 + b * NSET + i].reserve(sizes[i], &p[i])) != SPX_OK) return rc;
-        set[b].raw = (uint8_t*)p[0];
-        set[b].off = (uint64_t*)p[1];
-        set[b].dig = (uint8_t*)p[2];
-        set[b].dig_off = (uint64_t*)p[3];
-        set[b].len = p[4];
-        set[b].doc = p[5];
-        set[b].ptr = (uint64_t*)p[6];
-        set[b].out = (spv_vote*)p[7];
-    }
-    QuietOnError quiet(nullptr, true);  // (two streams: a failed call waits for the device)
-    const size_t npieces = cut.size() - 1;
-    auto copy_in = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        hipStream_t st = ix->assign_s[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1], a0 = offsets[q0], tc = offsets[q1] - a0;
-        const uint64_t* src = offsets + q0;
-        if (a0) {
-            s.h_off.resize(q1 - q0 + 1);
-            for (uint64_t q = q0; q <= q1; ++q) s.h_off[q - q0] = offsets[q] - a0;
-            src = s.h_off.data();
-        }
-        SPX_HIP(hipMemcpyAsync(s.off, src, (q1 - q0 + 1) * 8, hipMemcpyHostToDevice, st));
-        SPX_HIP(hipMemsetAsync(s.raw + tc, 0, raw_bytes - tc, st));
-        if (tc) SPX_HIP(hipMemcpyAsync(s.raw, seqs + a0, tc, hipMemcpyHostToDevice, st));
+    StageJob job;
+    job.mode = mode;
+    job.digest_kind = digest_kind;
+    job.k = k;
+    job.w = w;
+    job.seqs = seqs;
+    job.offsets = offsets;
+    job.nreads = nreads;
+    job.out_values = out_values;
+    job.want_docs = true;
+    StagePlan plan;
+    if ((rc = stage_streams(ix, job.streams)) != SPX_OK) return rc;
+    if ((rc = stage_plan(ix, job, &plan)) != SPX_OK) return rc;
+    void* d_out[2] = {};
+    for (int b = 0; b < plan.sets; ++b)
+        if ((rc = ix->vote_scr[spx_index::V_OUT0 + b].reserve((plan.worst_reads + 1) * sizeof(spv_vote), &d_out[b])) != SPX_OK) return rc;
+    job.wait = [](hipStream_t st) -> int {
+        SPX_HIP(hipStreamSynchronize(st));
         return SPX_OK;
     };
-    auto run = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        hipStream_t st = ix->assign_s[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1], nr = q1 - q0, tc = offsets[q1] - offsets[q0];
+    job.enqueue = [&](const StageView& v) -> int {
+        // what the piece's long reads hold (a digestion only shortens them): the size of their tables
         uint64_t piece_long_values = 0;
-        for (uint64_t q = q0; q < q1; ++q)
+        for (uint64_t q = v.q0; q < v.q0 + v.nreads; ++q)
             if (offsets[q + 1] - offsets[q] > MEDIUM_MAX) piece_long_values += offsets[q + 1] - offsets[q];
-        const uint64_t* voffs = s.off;
-        int r;
-        if (digest_kind) {
-            r = narrow ? spx_digest_query_batch_device16(ix, mode, digest_kind, k, w, s.raw, s.off, nr, tc, s.dig, dig_bytes, s.dig_off,
-                                                         (uint16_t*)s.len, s.ptr, (uint16_t*)s.doc, nullptr, 0, 0, st)
-                       : spx_digest_query_batch_device(ix, mode, digest_kind, k, w, s.raw, s.off, nr, tc, s.dig, dig_bytes, s.dig_off,
-                                                       (uint32_t*)s.len, s.ptr, (uint32_t*)s.doc, nullptr, 0, 0, st);
-            voffs = s.dig_off;
-        } else {
-            r = narrow ? spx_query_batch_device16(ix, mode, s.raw, s.off, nr, tc, (uint16_t*)s.len, s.ptr, (uint16_t*)s.doc, nullptr, 0,
-                                                  0, st)
-                       : spx_query_batch_device(ix, mode, s.raw, s.off, nr, tc, (uint32_t*)s.len, s.ptr, (uint32_t*)s.doc, nullptr, 0, 0,
-                                                st);
-        }
+        const int r = votes_enqueue(ix, v.lengths, v.docs, v.value_bits, v.offs, v.nreads, v.total_values, piece_long_values, min_length,
+                                    (spv_vote*)d_out[v.set], v.stream);
         if (r != SPX_OK) return r;
-        if ((r = votes_enqueue(ix, s.len, s.doc, narrow ? 16 : 32, voffs, nr, tc, piece_long_values, min_length, s.out, st)) != SPX_OK)
-            return r;
-        SPX_HIP(hipMemcpyAsync(out + q0, s.out, nr * sizeof(spv_vote), hipMemcpyDeviceToHost, st));
-        if (out_values && digest_kind) {
-            s.h_dig_off.resize(nr + 1);
-            SPX_HIP(hipMemcpyAsync(s.h_dig_off.data(), s.dig_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-        }
+        SPX_HIP(hipMemcpyAsync(out + v.q0, d_out[v.set], v.nreads * sizeof(spv_vote), hipMemcpyDeviceToHost, v.stream));
         return SPX_OK;
     };
-    auto finish = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1];
-        SPX_HIP(hipStreamSynchronize(ix->assign_s[c & 1]));
-        spx_walk_stats ws;
-        int r = spx_last_walk_stats(ix, &ws);
-        if (r != SPX_OK) return r;
-        if ((r = votes_collect(ix)) != SPX_OK) return r;
-        if ((r = vote_error_code(ix)) != SPX_OK) return r;
-        if (out_values)
-            for (uint64_t q = q0; q < q1; ++q)
-                out_values[q] = digest_kind ? s.h_dig_off[q - q0 + 1] - s.h_dig_off[q - q0] : offsets[q + 1] - offsets[q];
-        return SPX_OK;
+    job.collect = [&](const StageView&) -> int {
+        const int r = product_collect(ix, ix->votes, VOTE_WORDS, 6);
+        return r != SPX_OK ? r : vote_error_code(ix);
     };
-    for (size_t c = 0; c < npieces; ++c) {
-        if ((rc = copy_in(c)) != SPX_OK) return rc;
-        if (c && (rc = finish(c - 1)) != SPX_OK) return rc;
-        if ((rc = run(c)) != SPX_OK) return rc;
-    }
-    if ((rc = finish(npieces - 1)) != SPX_OK) return rc;
-    return quiet.done(SPX_OK);
+    QuietOnError quiet(nullptr, true);  // (two streams: a failed call waits for the device)
+    return quiet.done(stage_run(ix, job, plan));
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <functional>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/spumoni_gpu.h"
 #include "spx_layout.h"
@@ -258,22 +259,35 @@ struct spx_index {
     enum { C_DESC, C_ENDS, C_SEAMS, C_CKPT, C_FLAGS, C_FAIL, C_CNT, C_CUB, C_LEN_BITS, C_COUNT };
     Scratch chunk_scr[C_COUNT];
     Scratch digest_scr[NDIGSCR];  // spx_digest.hip (under mu): handed out in the order asked for, the last one to the scans
-    // document votes (spx_docvote.hip): counters, read lists and the long reads' tables (under mu), then the two buffer
-    // sets of spv_assign_batch's pipeline, V_SET_STRIDE slots each (under host_mu); the events around the vote kernels
-    // of the last call and what that call counted
-    enum { V_COUNTERS, V_MEDIUM, V_LONG, V_TILES, V_ACC, V_TABLE, V_SET0, V_SET_STRIDE = 8, V_COUNT = V_SET0 + 2 * V_SET_STRIDE };
+    // The staged walk (spx_stage.hip, under host_mu) under spv_assign_batch, spm_mems_begin and spp_place_batch: two buffer
+    // sets of the seven arrays a piece of reads needs on its way through digestion and walk, G_SET_STRIDE slots each, and
+    // the two streams the pieces of a batch alternate between.  One group for the three products: each holds host_mu for
+    // its whole call, and what a product keeps beyond its call (spm_mems_fetch: M_OUT, M_OUT_DOCS) is the product's own.
+    enum { G_RAW, G_OFFS, G_DIG, G_DIG_OFFS, G_LEN, G_DOC, G_PTR, G_SET_STRIDE, G_COUNT = 2 * G_SET_STRIDE };
+    Scratch stage_scr[G_COUNT];
+    hipStream_t stage_s[2] = {nullptr, nullptr};
+    // What a product's kernels count (product_enqueue / product_collect below, under mu): the device words they count in,
+    // zeroed in front of every launch -- the words that add up first, the error bits last --, the events around the
+    // kernels of the last call and the stream they ran on, and what the call has counted so far.
+    struct Product {
+        Scratch counters;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        hipStream_t stream = nullptr;
+        bool have = false, pending = false;
+        uint64_t acc[6] = {};
+        uint64_t error = 0;
+        float ms = 0;
+    };
+    // document votes (spx_docvote.hip): read lists and the long reads' tables (under mu), then the records of the staged
+    // walk's two buffer sets (under host_mu)
+    enum { V_MEDIUM, V_LONG, V_TILES, V_ACC, V_TABLE, V_OUT0, V_COUNT = V_OUT0 + 2 };
     Scratch vote_scr[V_COUNT];
-    hipEvent_t ev_v0 = nullptr, ev_v1 = nullptr;
-    hipStream_t vote_stream = nullptr, assign_s[2] = {nullptr, nullptr};
-    bool have_votes = false, vote_pending = false;
-    uint64_t vote_acc[6] = {};
-    uint64_t vote_error = 0;
-    float vote_ms = 0;
+    Product votes;  // acc: reads short, medium, long, empty; voting positions; tiles
     // matches (spx_mems.hip): counters, the bitmap of reported starts, its prefix sums and the scan's space (under mu),
-    // then spm_mems_begin's buffers (under host_mu); the events around the count and the write kernels of the last
-    // call, what that call counted, and the records that wait for spm_mems_fetch
-    enum { M_COUNTERS, M_BITS, M_PREFIX, M_CUB, M_RAW, M_OFFS, M_DIG, M_DIG_OFFS, M_LEN, M_PTR, M_DOC, M_MOFFS, M_OUT,
-           M_OUT_DOCS, M_COUNT };
+    // then spm_mems_begin's match offsets (under host_mu); the events around the count and the write kernels of the last
+    // call -- two intervals with a host wait between them --, what that call counted, and the records that wait for
+    // spm_mems_fetch
+    enum { M_COUNTERS, M_BITS, M_PREFIX, M_CUB, M_MOFFS, M_OUT, M_OUT_DOCS, M_COUNT };
     Scratch mems_scr[M_COUNT];
     hipEvent_t ev_m[4] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t mems_stream = nullptr;
@@ -281,17 +295,9 @@ struct spx_index {
     uint64_t mems_capacity = 0, mems_ready_n = 0;
     uint64_t mems_acc[4] = {};  // values, matches, longest, error bits
     float mems_ms = 0;
-    // placements (spx_place.hip): the counters (under mu), then the two buffer sets of spp_place_batch's pipeline,
-    // PL_SET_STRIDE slots each (under host_mu; its streams are assign_s); the events around the placement kernels of
-    // the last call and what that call counted
-    enum { PL_COUNTERS, PL_SET0, PL_SET_STRIDE = 8, PL_COUNT = PL_SET0 + 2 * PL_SET_STRIDE };
-    Scratch place_scr[PL_COUNT];
-    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
-    hipStream_t place_stream = nullptr;
-    bool have_place = false, place_pending = false;
-    uint64_t place_acc[4] = {};  // values, placed, seed values, extended values
-    uint64_t place_error = 0;
-    float place_ms = 0;
+    // placements (spx_place.hip): the records of the staged walk's two buffer sets (under host_mu)
+    Scratch place_scr[2];
+    Product place;  // acc: values, placed, seed values, extended values
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -346,6 +352,73 @@ inline void bind_view(spx_index* ix) {
 int ctx_stream_of(spx_index* ix, hipStream_t* out);
 int ctx_wait(spx_index* ix, hipStream_t st);
 int init_runtime(spx_index* ix);
+// ---- spx_stage.hip: the staged walk.  A batch of reads in host memory is cut into pieces of about 32 Mi characters that
+// alternate between two buffer sets and two streams: a piece's reads are copied in while the piece before is digested,
+// walked and handed to the product's kernels (queries on one index are serialised; the copies are not).  A piece is
+// finished -- its walk's and its product's counters read -- before the kernels of the next are enqueued.
+struct StageView {  // a piece behind its walk, on the device
+    const uint8_t* reads;  // the characters the values belong to: the digested reads under digestion
+    const uint64_t* offs;  // nreads + 1 offsets of the values (and of `reads`)
+    const void* lengths;   // value_bits wide
+    const uint64_t* pointers;  // MS mode, else null
+    const void* docs;          // when asked for, else null
+    uint64_t q0, nreads;       // the piece's reads are [q0, q0 + nreads) of the batch
+    uint64_t total_values;     // an upper bound: a digestion only shortens the reads
+    int value_bits, set;
+    hipStream_t stream;
+};
+struct StageJob {
+    int mode = SPX_MODE_MS, digest_kind = 0;
+    uint32_t k = 0, w = 0;
+    const uint8_t* seqs = nullptr;
+    const uint64_t* offsets = nullptr;
+    uint64_t nreads = 0;       // at least 1
+    uint64_t* out_values = nullptr;  // per read, the values it had (null: not wanted)
+    bool want_docs = false;
+    // the product's kernels read view.reads at view.offs: the digested reads are never parked while the call runs.  The
+    // others keep the index's own digest_parked (parking is a measured tuning of large batches)
+    bool reads_characters = false;
+    bool one_piece = false;    // the batch is one piece however large, on streams[0] alone
+    hipStream_t streams[2] = {nullptr, nullptr};
+    std::function<int(hipStream_t)> wait;            // the host waits for a piece's stream
+    std::function<int(const StageView&)> enqueue;    // the product's kernels and its copy-out, behind the piece's walk
+    std::function<int(const StageView&)> collect;    // after the wait and spx_last_walk_stats
+};
+struct StagePlan {
+    std::vector<uint64_t> cut;  // piece c is reads [cut[c], cut[c + 1])
+    uint64_t longest = 0, worst_chars = 0, worst_reads = 0, raw_bytes = 0, dig_bytes = 0;
+    bool narrow = true;  // 16-bit values: every read is below 65536 characters
+    int sets = 1;        // buffer sets in use: 2 when there is more than one piece
+    void* p[2][spx_index::G_SET_STRIDE] = {};  // null: not needed by this job
+};
+// checks the offsets, cuts the batch and reserves the buffer sets for the worst piece, before anything is enqueued (a
+// buffer that grows is freed first: a device-wide wait)
+int stage_plan(spx_index* ix, const StageJob& job, StagePlan* plan);
+int stage_streams(spx_index* ix, hipStream_t out[2]);  // the two streams of the pieces (created on first use)
+int stage_run(spx_index* ix, const StageJob& job, const StagePlan& plan);
+void release_stage(spx_index* ix);
+// A product's kernels between its two events.  The caller holds ix->mu and has set the device; `launch` gets the zeroed
+// counters.  The counters and the events are the index's: a call on another stream waits for the one before.
+template <typename Launch>
+int product_enqueue(spx_index::Product& p, size_t words, hipStream_t st, Launch&& launch) {
+    if (!p.ev0) SPX_HIP(hipEventCreate(&p.ev0));
+    if (!p.ev1) SPX_HIP(hipEventCreate(&p.ev1));
+    void* c = nullptr;
+    int rc;
+    if ((rc = p.counters.reserve(words * 8, &c)) != SPX_OK) return rc;
+    if (p.have && p.stream != st) SPX_HIP(hipStreamWaitEvent(st, p.ev1, 0));
+    SPX_HIP(hipMemsetAsync(c, 0, words * 8, st));
+    SPX_HIP(hipEventRecord(p.ev0, st));
+    if ((rc = launch(c)) != SPX_OK) return rc;
+    SPX_HIP(hipEventRecord(p.ev1, st));
+    p.have = p.pending = true;
+    p.stream = st;
+    return SPX_OK;
+}
+// waits for the kernels enqueued last and adds their first `nacc` words to p.acc, their last to p.error.  Takes ix->mu.
+int product_collect(spx_index* ix, spx_index::Product& p, int words, int nacc);
+void product_reset(spx_index* ix, spx_index::Product& p);
+void product_release(spx_index::Product& p);
 // spx_docvote.hip: frees what the document votes hold of the device (spx_index_free)
 void release_votes(spx_index* ix);
 // spx_mems.hip: the same for the matches

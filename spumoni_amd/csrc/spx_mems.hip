@@ -429,94 +429,58 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
         ix->mems_ready_docs = want_docs != 0;
         return SPX_OK;
     }
-    uint64_t longest = 0;
-    for (uint64_t q = 0; q < nreads; ++q) {
-        if (offsets[q + 1] < offsets[q]) {
-            set_error("offsets must not decrease (read %llu)", (unsigned long long)q);
-            return SPX_E_ARG;
-        }
-        longest = std::max(longest, offsets[q + 1] - offsets[q]);
-    }
-    if (longest >= (1ull << 32)) {
-        set_error("a read has 2^32 characters or more");
-        return SPX_E_ARG;
-    }
-    const bool narrow = longest < 65536;
-    const size_t width = narrow ? 2 : 4;
-    const uint64_t a0 = offsets[0], tc = offsets[nreads] - a0;
-    hipStream_t st = nullptr;
+    // the staged walk (spx_stage.hip) with exactly one piece, on the handle's stream: the count kernels behind the walk,
+    // and -- the host has waited and knows the number of records -- the write kernels
+    StageJob job;
+    job.digest_kind = digest_kind;
+    job.k = k;
+    job.w = w;
+    job.seqs = seqs;
+    job.offsets = offsets;
+    job.nreads = nreads;
+    job.out_values = out_values;
+    job.want_docs = want_docs != 0;
+    job.one_piece = true;
     int rc;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    const uint64_t raw_bytes = ((tc + 15) & ~15ull) + 64;
-    const uint64_t dig_bytes = digest_kind ? spx_digest_capacity(digest_kind, k, tc) + 32 : 0;
-    constexpr int NBUF = 8;
-    const int slots[NBUF] = {spx_index::M_RAW, spx_index::M_OFFS, spx_index::M_DIG, spx_index::M_DIG_OFFS,
-                             spx_index::M_LEN, spx_index::M_PTR, spx_index::M_DOC, spx_index::M_MOFFS};
-    const size_t sizes[NBUF] = {raw_bytes, (nreads + 1) * 8, dig_bytes, digest_kind ? (nreads + 1) * 8 : 0, (tc + 16) * width,
-                                (tc + 2) * 8, want_docs ? (tc + 16) * width : 0, (nreads + 1) * 8};
-    void* p[NBUF] = {};
-    for (int i = 0; i < NBUF; ++i)
-        if (sizes[i] && (rc = ix->mems_scr[slots[i]].reserve(sizes[i], &p[i])) != SPX_OK) return rc;
-    uint8_t *d_raw = (uint8_t*)p[0], *d_dig = (uint8_t*)p[2];
-    uint64_t *d_off = (uint64_t*)p[1], *d_dig_off = (uint64_t*)p[3], *d_ptr = (uint64_t*)p[5], *d_moffs = (uint64_t*)p[7];
-    void *d_len = p[4], *d_doc = p[6];
-    QuietOnError quiet(st);  // (a failed call leaves nothing reading seqs / offsets or writing the outputs)
-    std::vector<uint64_t> h_off;
-    const uint64_t* src = offsets;
-    if (a0) {
-        h_off.resize(nreads + 1);
-        for (uint64_t q = 0; q <= nreads; ++q) h_off[q] = offsets[q] - a0;
-        src = h_off.data();
-    }
-    SPX_HIP(hipMemcpyAsync(d_off, src, (nreads + 1) * 8, hipMemcpyHostToDevice, st));
-    SPX_HIP(hipMemsetAsync(d_raw + tc, 0, raw_bytes - tc, st));
-    if (tc) SPX_HIP(hipMemcpyAsync(d_raw, seqs + a0, tc, hipMemcpyHostToDevice, st));
-    const uint64_t* voffs = d_off;
-    if (digest_kind) {
-        rc = narrow ? spx_digest_query_batch_device16(ix, SPX_MODE_MS, digest_kind, k, w, d_raw, d_off, nreads, tc, d_dig, dig_bytes,
-                                                      d_dig_off, (uint16_t*)d_len, d_ptr, (uint16_t*)d_doc, nullptr, 0, 0, st)
-                    : spx_digest_query_batch_device(ix, SPX_MODE_MS, digest_kind, k, w, d_raw, d_off, nreads, tc, d_dig, dig_bytes,
-                                                    d_dig_off, (uint32_t*)d_len, d_ptr, (uint32_t*)d_doc, nullptr, 0, 0, st);
-        voffs = d_dig_off;
-    } else {
-        rc = narrow ? spx_query_batch_device16(ix, SPX_MODE_MS, d_raw, d_off, nreads, tc, (uint16_t*)d_len, d_ptr, (uint16_t*)d_doc,
-                                               nullptr, 0, 0, st)
-                    : spx_query_batch_device(ix, SPX_MODE_MS, d_raw, d_off, nreads, tc, (uint32_t*)d_len, d_ptr, (uint32_t*)d_doc, nullptr,
-                                             0, 0, st);
-    }
-    if (rc != SPX_OK) return rc;
+    if ((rc = ctx_stream_of(ix, &job.streams[0])) != SPX_OK) return rc;
+    hipStream_t st = job.streams[0];
+    StagePlan plan;
+    if ((rc = stage_plan(ix, job, &plan)) != SPX_OK) return rc;
+    void* d_moffs = nullptr;
+    if ((rc = ix->mems_scr[spx_index::M_MOFFS].reserve((nreads + 1) * 8, &d_moffs)) != SPX_OK) return rc;
     MemArgs a{};
-    a.L = (const uint4*)d_len;
-    a.P = d_ptr;
-    a.D = d_doc;
-    a.offs = voffs;
-    a.nreads = nreads;
-    a.min_length = min_length;
-    a.moffs = d_moffs;
-    if ((rc = mems_enqueue_count(ix, a, narrow ? 16 : 32, tc, st)) != SPX_OK) return rc;
-    SPX_HIP(hipMemcpyAsync(match_offsets, d_moffs, (nreads + 1) * 8, hipMemcpyDeviceToHost, st));
-    std::vector<uint64_t> h_dig_off;
-    if (out_values && digest_kind) {
-        h_dig_off.resize(nreads + 1);
-        SPX_HIP(hipMemcpyAsync(h_dig_off.data(), d_dig_off, (nreads + 1) * 8, hipMemcpyDeviceToHost, st));
-    }
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    spx_walk_stats ws;
-    if ((rc = spx_last_walk_stats(ix, &ws)) != SPX_OK) return rc;
-    // the records, at their exact size
-    const uint64_t n = match_offsets[nreads];
-    void *d_out = nullptr, *d_out_docs = nullptr;
-    if ((rc = ix->mems_scr[spx_index::M_OUT].reserve(n * sizeof(spm_match) + 16, &d_out)) != SPX_OK) return rc;
-    if (want_docs && (rc = ix->mems_scr[spx_index::M_OUT_DOCS].reserve(n * 4 + 16, &d_out_docs)) != SPX_OK) return rc;
-    a.out = (uint4*)d_out;
-    a.out_docs = (uint32_t*)d_out_docs;
-    a.cap = n;
-    if ((rc = mems_enqueue_write(ix, a, narrow ? 16 : 32, st)) != SPX_OK) return rc;
-    ix->mems_pending = true;
-    if ((rc = mems_collect(ix)) != SPX_OK) return rc;
-    if ((rc = mems_error_code(ix)) != SPX_OK) return rc;
-    if (out_values)
-        for (uint64_t q = 0; q < nreads; ++q) out_values[q] = digest_kind ? h_dig_off[q + 1] - h_dig_off[q] : offsets[q + 1] - offsets[q];
+    uint64_t n = 0;
+    job.wait = [&](hipStream_t s) -> int { return ctx_wait(ix, s); };
+    job.enqueue = [&](const StageView& v) -> int {
+        a.L = (const uint4*)v.lengths;
+        a.P = v.pointers;
+        a.D = v.docs;
+        a.offs = v.offs;
+        a.nreads = nreads;
+        a.min_length = min_length;
+        a.moffs = (uint64_t*)d_moffs;
+        const int r = mems_enqueue_count(ix, a, v.value_bits, v.total_values, st);
+        if (r != SPX_OK) return r;
+        SPX_HIP(hipMemcpyAsync(match_offsets, d_moffs, (nreads + 1) * 8, hipMemcpyDeviceToHost, st));
+        return SPX_OK;
+    };
+    job.collect = [&](const StageView& v) -> int {
+        // the records, at their exact size
+        n = match_offsets[nreads];
+        void *d_out = nullptr, *d_out_docs = nullptr;
+        int r;
+        if ((r = ix->mems_scr[spx_index::M_OUT].reserve(n * sizeof(spm_match) + 16, &d_out)) != SPX_OK) return r;
+        if (want_docs && (r = ix->mems_scr[spx_index::M_OUT_DOCS].reserve(n * 4 + 16, &d_out_docs)) != SPX_OK) return r;
+        a.out = (uint4*)d_out;
+        a.out_docs = (uint32_t*)d_out_docs;
+        a.cap = n;
+        if ((r = mems_enqueue_write(ix, a, v.value_bits, st)) != SPX_OK) return r;
+        ix->mems_pending = true;
+        if ((r = mems_collect(ix)) != SPX_OK) return r;
+        return mems_error_code(ix);
+    };
+    QuietOnError quiet(st);  // (a failed call leaves nothing reading seqs / offsets or writing the outputs)
+    if ((rc = stage_run(ix, job, plan)) != SPX_OK) return rc;
     *n_matches = n;
     ix->mems_ready = true;
     ix->mems_ready_n = n;

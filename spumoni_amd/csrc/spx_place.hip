@@ -37,6 +37,7 @@ struct PlaceCounters {  // device; zeroed in front of every launch
     unsigned long long values, placed, seed_values, extended_values;
     unsigned long long error;  // bit 0: a read of 2^32 values or more, or decreasing offsets; bit 1: more values than total_values said
 };
+constexpr int PLACE_WORDS = sizeof(PlaceCounters) / 8;  // (the first four are what spp_place_stats reports, the last the error)
 struct PlaceArgs {
     const uint8_t* R;
     const uint4* L;
@@ -337,61 +338,26 @@ __global__ __launch_bounds__(256) void k_place(PlaceArgs a) {
 int place_enqueue(spx_index* ix, PlaceArgs& a, int value_bits, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    if (!ix->ev_p0) SPX_HIP(hipEventCreate(&ix->ev_p0));
-    if (!ix->ev_p1) SPX_HIP(hipEventCreate(&ix->ev_p1));
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->place_scr[spx_index::PL_COUNTERS].reserve(sizeof(PlaceCounters), &p)) != SPX_OK) return rc;
-    a.c = (PlaceCounters*)p;
     a.T = ix->text;
     a.n_text = ix->n_text;
-    // the counters and the events are the index's: a call on another stream waits for the one before
-    if (ix->have_place && ix->place_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_p1, 0));
-    SPX_HIP(hipMemsetAsync(a.c, 0, sizeof(PlaceCounters), st));
-    SPX_HIP(hipEventRecord(ix->ev_p0, st));
-    if (a.nreads) {
+    return product_enqueue(ix->place, PLACE_WORDS, st, [&](void* counters) -> int {
+        a.c = (PlaceCounters*)counters;
+        if (!a.nreads) return SPX_OK;
         const unsigned grid = (unsigned)std::min<uint64_t>((a.nreads + 15) / 16, 8192);
         if (value_bits == 16)
             k_place<16><<<grid, 256, 0, st>>>(a);
         else
             k_place<32><<<grid, 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
-    }
-    SPX_HIP(hipEventRecord(ix->ev_p1, st));
-    ix->have_place = true;
-    ix->place_stream = st;
-    return SPX_OK;
-}
-
-// Waits for the placement kernel enqueued last and adds what it counted to ix->place_acc / place_ms.  Takes ix->mu.
-int place_collect(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventSynchronize(ix->ev_p1));
-    PlaceCounters c;
-    SPX_HIP(hipMemcpy(&c, ix->place_scr[spx_index::PL_COUNTERS].p, sizeof c, hipMemcpyDeviceToHost));
-    float ms = 0;
-    SPX_HIP(hipEventElapsedTime(&ms, ix->ev_p0, ix->ev_p1));
-    const unsigned long long v[4] = {c.values, c.placed, c.seed_values, c.extended_values};
-    for (int i = 0; i < 4; ++i) ix->place_acc[i] += v[i];
-    ix->place_ms += ms;
-    ix->place_error |= c.error;
-    ix->place_pending = false;
-    return SPX_OK;
-}
-void place_reset(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->place_acc, 0, sizeof ix->place_acc);
-    ix->place_ms = 0;
-    ix->place_error = 0;
-    ix->place_pending = false;
+        return SPX_OK;
+    });
 }
 int place_error_code(const spx_index* ix) {
-    if (ix->place_error & 1) {
+    if (ix->place.error & 1) {
         set_error("a read has 2^32 values or more (or its offsets decrease): the placements take reads below that");
         return SPX_E_FORMAT;
     }
-    if (ix->place_error & 2) {
+    if (ix->place.error & 2) {
         set_error("the batch holds more values than total_values said: the reads behind it are not placed");
         return SPX_E_FORMAT;
     }
@@ -423,8 +389,7 @@ int check_params(const spx_index* ix, uint64_t min_seed, uint32_t mismatch_penal
 void release_place(spx_index* ix) {
     for (auto& sc : ix->place_scr)
         if (sc.p) (void)hipFree(sc.p);
-    if (ix->ev_p0) (void)hipEventDestroy(ix->ev_p0);
-    if (ix->ev_p1) (void)hipEventDestroy(ix->ev_p1);
+    product_release(ix->place);
 }
 
 }  // namespace spx
@@ -457,7 +422,7 @@ int spp_place_device(spx_index* ix, const uint8_t* d_seqs, const void* d_lengths
                   "8-byte and d_docs to its values");
         return SPX_E_ARG;
     }
-    place_reset(ix);
+    product_reset(ix, ix->place);
     PlaceArgs a{};
     a.R = d_seqs;
     a.L = (const uint4*)d_lengths;
@@ -470,9 +435,7 @@ int spp_place_device(spx_index* ix, const uint8_t* d_seqs, const void* d_lengths
     a.penalty = (int32_t)mismatch_penalty;
     a.x_drop = (int64_t)x_drop;
     a.out = (uint4*)d_out;
-    rc = place_enqueue(ix, a, value_bits, (hipStream_t)stream);
-    if (rc == SPX_OK) ix->place_pending = true;
-    return rc;
+    return place_enqueue(ix, a, value_bits, (hipStream_t)stream);
 }
 
 int spp_last_place_stats(spx_index* ix, spp_place_stats* out) {
@@ -480,25 +443,24 @@ int spp_last_place_stats(spx_index* ix, spp_place_stats* out) {
         set_error("null argument");
         return SPX_E_ARG;
     }
-    if (!ix->have_place) {
+    if (!ix->place.have) {
         set_error("no placements have been computed on this index yet");
         return SPX_E_ARG;
     }
-    if (ix->place_pending) {
-        const int rc = place_collect(ix);
+    if (ix->place.pending) {
+        const int rc = product_collect(ix, ix->place, PLACE_WORDS, 4);
         if (rc != SPX_OK) return rc;
     }
-    out->values = ix->place_acc[0];
-    out->placed = ix->place_acc[1];
-    out->seed_values = ix->place_acc[2];
-    out->extended_values = ix->place_acc[3];
-    out->kernel_ms = ix->place_ms;
+    out->values = ix->place.acc[0];
+    out->placed = ix->place.acc[1];
+    out->seed_values = ix->place.acc[2];
+    out->extended_values = ix->place.acc[3];
+    out->kernel_ms = ix->place.ms;
     return place_error_code(ix);
 }
 
-// Pieces of about PIECE_CHARS characters alternate between two buffer sets and two streams, as in spv_assign_batch: a
-// piece's reads are copied in while the piece before is digested, walked and placed.  A piece is finished -- its walk's
-// and placements' counters read -- before the kernels of the next are enqueued.
+// The staged walk (spx_stage.hip) with the placement kernel behind every piece's walk.  The kernel reads the digested
+// reads at the offsets of the concatenation: the one product that sets reads_characters.
 int spp_place_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
                     uint64_t nreads, uint64_t min_seed, uint32_t mismatch_penalty, uint64_t x_drop, int want_docs,
                     spp_placement* out, uint64_t* out_values) {
@@ -526,147 +488,55 @@ int spp_place_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
-    place_reset(ix);
+    product_reset(ix, ix->place);
     if (nreads == 0) {
-        ix->have_place = true;  // (the stats of an empty batch are zeros)
+        ix->place.have = true;  // (the stats of an empty batch are zeros)
         return SPX_OK;
     }
-    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
-    std::vector<uint64_t> cut{0};
-    uint64_t longest = 0, worst_chars = 0, worst_reads = 0;
-    for (uint64_t q = 0; q < nreads; ++q) {
-        if (offsets[q + 1] < offsets[q]) {
-            set_error("offsets must not decrease (read %llu)", (unsigned long long)q);
-            return SPX_E_ARG;
-        }
-        longest = std::max(longest, offsets[q + 1] - offsets[q]);
-        const uint64_t q0 = cut.back();
-        if (q + 1 == nreads || offsets[q + 1] - offsets[q0] >= PIECE_CHARS || q + 1 - q0 >= PIECE_READS) {
-            worst_chars = std::max(worst_chars, offsets[q + 1] - offsets[q0]);
-            worst_reads = std::max(worst_reads, q + 1 - q0);
-            cut.push_back(q + 1);
-        }
-    }
-    if (longest >= (1ull << 32)) {
-        set_error("a read has 2^32 characters or more");
-        return SPX_E_ARG;
-    }
-    const bool narrow = longest < 65536;
-    const size_t width = narrow ? 2 : 4;
-    for (auto& st : ix->assign_s)
-        if (!st) SPX_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // both buffer sets, sized for the largest piece before anything is enqueued (growing one frees it: a device-wide wait)
-    const uint64_t raw_bytes = ((worst_chars + 15) & ~15ull) + 64;
-    const uint64_t dig_bytes = digest_kind ? spx_digest_capacity(digest_kind, k, worst_chars) + 32 : 0;
-    struct Set {
-        uint8_t *raw, *dig;
-        uint64_t *off, *dig_off, *ptr;
-        void *len, *doc;
-        spp_placement* out;
-        std::vector<uint64_t> h_off, h_dig_off;
-    } set[2];
-    for (int b = 0; b < 2 && (b == 0 || cut.size() > 2); ++b) {
-        constexpr int NSET = spx_index::PL_SET_STRIDE;
-        const size_t sizes[NSET] = {raw_bytes, (worst_reads + 1) * 8, dig_bytes, digest_kind ? (worst_reads + 1) * 8 : 0,
-                                    (worst_chars + 16) * width, want_docs ? (worst_chars + 16) * width : 0, (worst_chars + 2) * 8,
-                                    (worst_reads + 1) * sizeof(spp_placement)};
-        void* p[NSET] = {};
-        for (int i = 0; i < NSET; ++i)
-            if (sizes[i] && (rc = ix->place_scr[spx_index::PL_SET0 + b * NSET + i].reserve(sizes[i], &p[i])) != SPX_OK) return rc;
-        set[b].raw = (uint8_t*)p[0];
-        set[b].off = (uint64_t*)p[1];
-        set[b].dig = (uint8_t*)p[2];
-        set[b].dig_off = (uint64_t*)p[3];
-        set[b].len = p[4];
-        set[b].doc = p[5];
-        set[b].ptr = (uint64_t*)p[6];
-        set[b].out = (spp_placement*)p[7];
-    }
-    QuietOnError quiet(nullptr, true);  // (two streams: a failed call waits for the device)
-    // the kernels read the digested reads at the offsets of the concatenation: never parked while this call runs
-    struct Unparked {
-        spx_index* ix;
-        int before;
-        explicit Unparked(spx_index* i) : ix(i), before(i->digest_parked) { ix->digest_parked = 1; }
-        ~Unparked() { ix->digest_parked = before; }
-    } unparked(ix);
-    const size_t npieces = cut.size() - 1;
-    auto copy_in = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        hipStream_t st = ix->assign_s[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1], a0 = offsets[q0], tc = offsets[q1] - a0;
-        const uint64_t* src = offsets + q0;
-        if (a0) {
-            s.h_off.resize(q1 - q0 + 1);
-            for (uint64_t q = q0; q <= q1; ++q) s.h_off[q - q0] = offsets[q] - a0;
-            src = s.h_off.data();
-        }
-        SPX_HIP(hipMemcpyAsync(s.off, src, (q1 - q0 + 1) * 8, hipMemcpyHostToDevice, st));
-        SPX_HIP(hipMemsetAsync(s.raw + tc, 0, raw_bytes - tc, st));
-        if (tc) SPX_HIP(hipMemcpyAsync(s.raw, seqs + a0, tc, hipMemcpyHostToDevice, st));
+    StageJob job;
+    job.digest_kind = digest_kind;
+    job.k = k;
+    job.w = w;
+    job.seqs = seqs;
+    job.offsets = offsets;
+    job.nreads = nreads;
+    job.out_values = out_values;
+    job.want_docs = want_docs != 0;
+    job.reads_characters = true;
+    StagePlan plan;
+    if ((rc = stage_streams(ix, job.streams)) != SPX_OK) return rc;
+    if ((rc = stage_plan(ix, job, &plan)) != SPX_OK) return rc;
+    void* d_out[2] = {};
+    for (int b = 0; b < plan.sets; ++b)
+        if ((rc = ix->place_scr[b].reserve((plan.worst_reads + 1) * sizeof(spp_placement), &d_out[b])) != SPX_OK) return rc;
+    job.wait = [](hipStream_t st) -> int {
+        SPX_HIP(hipStreamSynchronize(st));
         return SPX_OK;
     };
-    auto run = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        hipStream_t st = ix->assign_s[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1], nr = q1 - q0, tc = offsets[q1] - offsets[q0];
+    job.enqueue = [&](const StageView& v) -> int {
         PlaceArgs a{};
-        a.R = s.raw;
-        a.offs = s.off;
-        int r;
-        if (digest_kind) {
-            r = narrow ? spx_digest_query_batch_device16(ix, SPX_MODE_MS, digest_kind, k, w, s.raw, s.off, nr, tc, s.dig, dig_bytes,
-                                                         s.dig_off, (uint16_t*)s.len, s.ptr, (uint16_t*)s.doc, nullptr, 0, 0, st)
-                       : spx_digest_query_batch_device(ix, SPX_MODE_MS, digest_kind, k, w, s.raw, s.off, nr, tc, s.dig, dig_bytes,
-                                                       s.dig_off, (uint32_t*)s.len, s.ptr, (uint32_t*)s.doc, nullptr, 0, 0, st);
-            a.R = s.dig;
-            a.offs = s.dig_off;
-        } else {
-            r = narrow ? spx_query_batch_device16(ix, SPX_MODE_MS, s.raw, s.off, nr, tc, (uint16_t*)s.len, s.ptr, (uint16_t*)s.doc, nullptr,
-                                                  0, 0, st)
-                       : spx_query_batch_device(ix, SPX_MODE_MS, s.raw, s.off, nr, tc, (uint32_t*)s.len, s.ptr, (uint32_t*)s.doc, nullptr, 0,
-                                                0, st);
-        }
-        if (r != SPX_OK) return r;
-        a.L = (const uint4*)s.len;
-        a.P = s.ptr;
-        a.D = s.doc;
-        a.nreads = nr;
-        a.total_values = tc;  // (a digestion only shortens the reads)
+        a.R = v.reads;
+        a.L = (const uint4*)v.lengths;
+        a.P = v.pointers;
+        a.D = v.docs;
+        a.offs = v.offs;
+        a.nreads = v.nreads;
+        a.total_values = v.total_values;
         a.min_seed = min_seed;
         a.penalty = (int32_t)mismatch_penalty;
         a.x_drop = (int64_t)x_drop;
-        a.out = (uint4*)s.out;
-        if ((r = place_enqueue(ix, a, narrow ? 16 : 32, st)) != SPX_OK) return r;
-        ix->place_pending = true;
-        SPX_HIP(hipMemcpyAsync(out + q0, s.out, nr * sizeof(spp_placement), hipMemcpyDeviceToHost, st));
-        if (out_values && digest_kind) {
-            s.h_dig_off.resize(nr + 1);
-            SPX_HIP(hipMemcpyAsync(s.h_dig_off.data(), s.dig_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-        }
-        return SPX_OK;
-    };
-    auto finish = [&](size_t c) -> int {
-        Set& s = set[c & 1];
-        const uint64_t q0 = cut[c], q1 = cut[c + 1];
-        SPX_HIP(hipStreamSynchronize(ix->assign_s[c & 1]));
-        spx_walk_stats ws;
-        int r = spx_last_walk_stats(ix, &ws);
+        a.out = (uint4*)d_out[v.set];
+        const int r = place_enqueue(ix, a, v.value_bits, v.stream);
         if (r != SPX_OK) return r;
-        if ((r = place_collect(ix)) != SPX_OK) return r;
-        if ((r = place_error_code(ix)) != SPX_OK) return r;
-        if (out_values)
-            for (uint64_t q = q0; q < q1; ++q)
-                out_values[q] = digest_kind ? s.h_dig_off[q - q0 + 1] - s.h_dig_off[q - q0] : offsets[q + 1] - offsets[q];
+        SPX_HIP(hipMemcpyAsync(out + v.q0, d_out[v.set], v.nreads * sizeof(spp_placement), hipMemcpyDeviceToHost, v.stream));
         return SPX_OK;
     };
-    for (size_t c = 0; c < npieces; ++c) {
-        if ((rc = copy_in(c)) != SPX_OK) return rc;
-        if (c && (rc = finish(c - 1)) != SPX_OK) return rc;
-        if ((rc = run(c)) != SPX_OK) return rc;
-    }
-    if ((rc = finish(npieces - 1)) != SPX_OK) return rc;
-    return quiet.done(SPX_OK);
+    job.collect = [&](const StageView&) -> int {
+        const int r = product_collect(ix, ix->place, PLACE_WORDS, 4);
+        return r != SPX_OK ? r : place_error_code(ix);
+    };
+    QuietOnError quiet(nullptr, true);  // (two streams: a failed call waits for the device)
+    return quiet.done(stage_run(ix, job, plan));
 }
 
 }  // extern "C"

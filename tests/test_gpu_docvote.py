@@ -367,3 +367,28 @@ def test_cli_assign_refuses_an_index_without_doc(gpu, tmp_path):
     a = _cli(["assign", "-r", str(work / "ref"), "-p", str(work / "reads.fa"), "-n", "-P"], dict(os.environ))
     assert a.returncode == 1 and b"ref.fa.doc) is not present, so it cannot be used." in a.stderr
     assert not os.path.exists(work / "reads.fa.assignments")
+
+
+def test_cli_assign_keeps_what_is_in_front_of_a_failing_read(gpu, tmp_path):
+    """A read without characters ends the run as it ends `run`: what is in front of it is assigned and written first,
+    and the summary by document is not."""
+    work = tmp_path / "c"
+    shutil.copytree(os.path.join(FILES, "dna_multiline_fasta"), work)
+    text = open(work / "ref.fa.rawtext", "rb").read()
+    good = b"".join(b">r%d\n" % q + text[17 * q: 17 * q + 60] + b"\n" for q in range(40))
+    env = dict(os.environ, SPUMONI_TEXT=str(work / "ref.fa.rawtext"), SPUMONI_SUPER_BATCH="1000")
+    args = ["assign", "-r", str(work / "ref"), "-p", str(work / "reads.fa"), "-n", "-P", "-T", "2"]
+    with open(work / "reads.fa", "wb") as f:
+        f.write(good)
+    a = _cli(args, env)
+    assert a.returncode == 0, a.stderr.decode()
+    want = open(work / "reads.fa.assignments", "rb").read()
+    assert want.count(b"\n") == 40 and os.path.exists(work / "reads.fa.assignments.by_doc")
+    os.remove(work / "reads.fa.assignments")
+    os.remove(work / "reads.fa.assignments.by_doc")
+    with open(work / "reads.fa", "wb") as f:
+        f.write(good + b">bad_one\n>after\n" + text[:40] + b"\n")
+    a = _cli(args, env)
+    assert a.returncode == 1 and b"bad_one was empty after digestion" in a.stderr, a.stderr.decode()
+    assert open(work / "reads.fa.assignments", "rb").read() == want
+    assert not os.path.exists(work / "reads.fa.assignments.by_doc")
