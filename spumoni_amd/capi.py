@@ -617,6 +617,54 @@ class Index:
         _check(_spp().spp_last_place_stats(self._h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SppPlaceStats._fields_}
 
+    # -- chains (include/spumoni_chain.h) -------------------------------------------
+    def chain_device(self, d_matches, d_match_offsets, params=None, d_match_docs=None, d_out=None, d_out_score=None,
+                     d_out_pred=None, stream=None):
+        """One record per read (spc_chain, chain.CHAIN_DTYPE: the best collinear chain of the read's matches) from the
+        records mems_device left on the device: d_matches int32 (n, 4), d_match_offsets int64[reads + 1] (its first entry
+        need not be 0), d_match_docs int32[n] or None.  Returns d_out, an int32 tensor of shape (reads, 12); d_out_score /
+        d_out_pred (int32[n], optional) get f and pred of every anchor.  params: (lookback, max_dist, max_gap,
+        gap_penalty) or None for the defaults."""
+        import torch
+
+        from .chain import ChainParams
+
+        L = _spc()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_match_offsets.numel() - 1
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 12), dtype=torch.int32, device=d_match_offsets.device)
+        if d_matches.numel() == 0:  # (no anchors at all: the library still wants an address)
+            d_matches = torch.zeros((1, 4), dtype=torch.int32, device=d_match_offsets.device)
+        p = SpcParams(*(int(v) for v in (ChainParams() if params is None else params)))
+        _check(L.spc_chain_device(self._h, _t_ptr(d_matches), _t_ptr(d_match_docs), _t_ptr(d_match_offsets), nreads, C.byref(p),
+                                  _t_ptr(d_out), _t_ptr(d_out_score), _t_ptr(d_out_pred), C.c_void_p(st.cuda_stream)))
+        return d_out
+
+    def chain_host(self, seqs, offs, min_length, params=None, digest=None, want_docs=False):
+        """spc_chain_batch: reads in, (records chain.CHAIN_DTYPE[reads], values uint64[reads]) out; values = the read's
+        positions after digestion.  digest: (kind, k, w) or None; params as in chain_device."""
+        from .chain import CHAIN_DTYPE, ChainParams
+
+        L = _spc()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=CHAIN_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        p = SpcParams(*(int(v) for v in (ChainParams() if params is None else params)))
+        _check(L.spc_chain_batch(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                 C.byref(p), _np_ptr(rec), _np_ptr(vals)))
+        return rec[:nreads], vals[:nreads]
+
+    def chain_stats(self) -> dict:
+        """Of the most recent chain_device / chain_host call: reads, anchors, chained reads, the anchors in their chains,
+        the eligible pairs evaluated, kernel time."""
+        s = SpcChainStats()
+        _check(_spc().spc_last_chain_stats(self._h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in SpcChainStats._fields_}
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -747,6 +795,35 @@ def _spp() -> C.CDLL:
         L.spp_place_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, u32, u64, i32, vp, vp]
         L.spp_last_place_stats.argtypes = [vp, C.POINTER(SppPlaceStats)]
         _SPP_READY = True
+    return L
+
+
+# ---- the chains (include/spumoni_chain.h) ---------------------------------------------------------------------------
+CHAIN_EXPORTS = ["spc_chain_device", "spc_chain_batch", "spc_last_chain_stats"]
+_SPC_READY = False
+
+
+class SpcParams(C.Structure):
+    _fields_ = [("lookback", C.c_uint32), ("max_dist", C.c_uint32), ("max_gap", C.c_uint32), ("gap_penalty", C.c_uint32)]
+
+
+class SpcChainStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("anchors", C.c_uint64), ("chained_reads", C.c_uint64), ("chain_anchors", C.c_uint64),
+                ("candidates", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
+def _spc() -> C.CDLL:
+    """The library with the spc_* argtypes set (on first use)."""
+    global _SPC_READY
+    L = lib()
+    if not hasattr(L, "spc_chain_batch"):
+        raise SpxError(f"{LIB_PATH} has no chain kernel (spc_chain_batch): there is no CPU fallback")
+    if not _SPC_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spc_chain_device.argtypes = [vp, vp, vp, vp, u64, C.POINTER(SpcParams), vp, vp, vp, vp]
+        L.spc_chain_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), vp, vp]
+        L.spc_last_chain_stats.argtypes = [vp, C.POINTER(SpcChainStats)]
+        _SPC_READY = True
     return L
 
 

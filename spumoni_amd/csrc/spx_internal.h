@@ -298,6 +298,10 @@ struct spx_index {
     // placements (spx_place.hip): the records of the staged walk's two buffer sets (under host_mu)
     Scratch place_scr[2];
     Product place;  // acc: values, placed, seed values, extended values
+    // chains (spx_chain.hip): the records of spc_chain_batch (under host_mu); its matches are spm_mems_begin's, in mems_scr
+    enum { H_OUT, H_COUNT };
+    Scratch chain_scr[H_COUNT];
+    Product chain;  // acc: reads, anchors, chained reads, chain anchors, candidates
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -425,6 +429,23 @@ void release_votes(spx_index* ix);
 void release_mems(spx_index* ix);
 // spx_place.hip: the same for the placements
 void release_place(spx_index* ix);
+// spx_chain.hip: the same for the chains
+void release_chain(spx_index* ix);
+// spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
+// count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
+// device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on
+// m.stream; the call returns when that stream has been waited for.  The records stay in mems_scr (M_MOFFS, M_OUT,
+// M_OUT_DOCS) as they do for spm_mems_fetch.  The caller holds host_mu, has set the device and passes nreads >= 1.
+struct MemsOnDevice {
+    const uint64_t* match_offsets;  // nreads + 1
+    const void* records;            // n spm_match
+    const uint32_t* docs;           // n ids, null unless asked for
+    uint64_t nreads, n;
+    hipStream_t stream;
+};
+int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
+                      uint64_t nreads, uint64_t min_length, int want_docs, uint64_t* match_offsets, uint64_t* out_values,
+                      uint64_t* n_matches, const std::function<int(const MemsOnDevice&)>& then);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
 int build_fat(spx_index* ix);
 // spx_walk.hip: MS text against the index: text[samples_start[k]] must be the head of run k

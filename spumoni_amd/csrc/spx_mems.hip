@@ -429,6 +429,20 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
         ix->mems_ready_docs = want_docs != 0;
         return SPX_OK;
     }
+    return mems_begin_staged(ix, digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, match_offsets, out_values,
+                             n_matches, {});
+}
+
+}  // extern "C"
+
+namespace spx {
+
+int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
+                      uint64_t nreads, uint64_t min_length, int want_docs, uint64_t* match_offsets, uint64_t* out_values,
+                      uint64_t* n_matches, const std::function<int(const MemsOnDevice&)>& then) {
+    mems_reset(ix);
+    *n_matches = 0;
+    match_offsets[0] = 0;
     // the staged walk (spx_stage.hip) with exactly one piece, on the handle's stream: the count kernels behind the walk,
     // and -- the host has waited and knows the number of records -- the write kernels
     StageJob job;
@@ -476,7 +490,10 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
         a.cap = n;
         if ((r = mems_enqueue_write(ix, a, v.value_bits, st)) != SPX_OK) return r;
         ix->mems_pending = true;
+        if (then && (r = then(MemsOnDevice{(const uint64_t*)d_moffs, d_out, (const uint32_t*)d_out_docs, nreads, n, st})) != SPX_OK)
+            return r;
         if ((r = mems_collect(ix)) != SPX_OK) return r;
+        if (then && (r = ctx_wait(ix, st)) != SPX_OK) return r;
         return mems_error_code(ix);
     };
     QuietOnError quiet(st);  // (a failed call leaves nothing reading seqs / offsets or writing the outputs)
@@ -487,6 +504,10 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
     ix->mems_ready_docs = want_docs != 0;
     return quiet.done(SPX_OK);
 }
+
+}  // namespace spx
+
+extern "C" {
 
 int spm_mems_fetch(spx_index* ix, spm_match* out, uint32_t* out_docs) {
     if (!ix) {
