@@ -665,6 +665,66 @@ class Index:
         _check(_spc().spc_last_chain_stats(self._h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SpcChainStats._fields_}
 
+    # -- alignments (include/spumoni_align.h) ---------------------------------------
+    def align_device(self, d_reads, d_read_offsets, d_matches, d_match_offsets, d_chains, d_pred, params=None, gap_capacity=None,
+                     d_out=None, d_out_gap_offsets=None, d_out_gaps=None, stream=None):
+        """One record per read (spa_alignment, align.ALIGN_DTYPE: the read aligned along its best chain, every gap between
+        two anchors filled by an edit-distance table) from what mems_device and chain_device left on the device: d_reads
+        uint8 with d_read_offsets int64[reads + 1], d_matches int32 (n, 4) with d_match_offsets int64[reads + 1], d_chains
+        int32 (reads, 12) and d_pred int32[n] (chain_device's d_out and d_out_pred).  Returns (d_out int32 (reads, 12),
+        d_out_gap_offsets int64[reads + 1], d_out_gaps int32 (gap_capacity, 4)); gap_capacity defaults to the number of
+        matches, which always suffices.  params: (max_fill,) or None for the default."""
+        import torch
+
+        from .align import AlignParams
+
+        L = _spa()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = d_match_offsets.device
+        nreads = d_match_offsets.numel() - 1
+        if gap_capacity is None:
+            gap_capacity = d_matches.numel() // 4
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 12), dtype=torch.int32, device=dev)
+        if d_out_gap_offsets is None:
+            d_out_gap_offsets = torch.empty(max(nreads, 0) + 1, dtype=torch.int64, device=dev)
+        if d_out_gaps is None:
+            d_out_gaps = torch.empty((max(int(gap_capacity), 1), 4), dtype=torch.int32, device=dev)
+        p = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        _check(L.spa_align_device(self._h, _t_ptr(d_reads), _t_ptr(d_read_offsets), _t_ptr(d_matches), _t_ptr(d_match_offsets), nreads,
+                                  _t_ptr(d_chains), _t_ptr(d_pred), C.byref(p), int(gap_capacity), _t_ptr(d_out),
+                                  _t_ptr(d_out_gap_offsets), _t_ptr(d_out_gaps), C.c_void_p(st.cuda_stream)))
+        return d_out, d_out_gap_offsets, d_out_gaps
+
+    def align_host(self, seqs, offs, min_length, chain_params=None, params=None, digest=None, want_docs=False):
+        """spa_align_batch: reads in, (records align.ALIGN_DTYPE[reads], chains chain.CHAIN_DTYPE[reads], values
+        uint64[reads]) out; values = the read's positions after digestion.  digest: (kind, k, w) or None."""
+        from .align import ALIGN_DTYPE, AlignParams
+        from .chain import CHAIN_DTYPE, ChainParams
+
+        L = _spa()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=ALIGN_DTYPE)
+        chains = np.zeros(max(nreads, 1), dtype=CHAIN_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        _check(L.spa_align_batch(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                 C.byref(cp), C.byref(ap), _np_ptr(rec), _np_ptr(chains), _np_ptr(vals)))
+        return rec[:nreads], chains[:nreads], vals[:nreads]
+
+    def align_stats(self) -> dict:
+        """Of the most recent align_device / align_host call: reads, aligned reads, their gaps, the filled ones, table cells,
+        the error and overflow flags, kernel time and the time of the four steps (count and scan, walk, fill, reduce)."""
+        s = SpaAlignStats()
+        _check(_spa().spa_last_align_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpaAlignStats._fields_}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -824,6 +884,36 @@ def _spc() -> C.CDLL:
         L.spc_chain_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), vp, vp]
         L.spc_last_chain_stats.argtypes = [vp, C.POINTER(SpcChainStats)]
         _SPC_READY = True
+    return L
+
+
+# ---- the alignments (include/spumoni_align.h) -----------------------------------------------------------------------
+ALIGN_EXPORTS = ["spa_align_device", "spa_align_batch", "spa_last_align_stats"]
+_SPA_READY = False
+
+
+class SpaParams(C.Structure):
+    _fields_ = [("max_fill", C.c_uint32)]
+
+
+class SpaAlignStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("aligned_reads", C.c_uint64), ("gaps", C.c_uint64), ("filled_gaps", C.c_uint64),
+                ("cells", C.c_uint64), ("error", C.c_uint32), ("overflow", C.c_uint32), ("kernel_ms", C.c_float),
+                ("step_ms", C.c_float * 4)]
+
+
+def _spa() -> C.CDLL:
+    """The library with the spa_* argtypes set (on first use)."""
+    global _SPA_READY
+    L = lib()
+    if not hasattr(L, "spa_align_batch"):
+        raise SpxError(f"{LIB_PATH} has no align kernels (spa_align_batch): there is no CPU fallback")
+    if not _SPA_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spa_align_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, C.POINTER(SpaParams), u64, vp, vp, vp, vp]
+        L.spa_align_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams), vp, vp, vp]
+        L.spa_last_align_stats.argtypes = [vp, C.POINTER(SpaAlignStats)]
+        _SPA_READY = True
     return L
 
 

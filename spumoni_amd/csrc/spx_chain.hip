@@ -252,7 +252,16 @@ int chain_error_code(const spx_index* ix) {
     return SPX_OK;
 }
 
-int check_params(const spx_index* ix, const spc_params* p) {
+void set_params(ChainArgs& a, const spc_params& p) {
+    a.lookback = p.lookback;
+    a.max_dist = p.max_dist;
+    a.max_gap = p.max_gap;
+    a.gap_penalty = p.gap_penalty;
+}
+
+}  // namespace
+
+int chain_check_params(const spx_index* ix, const spc_params* p) {
     if (!ix) {
         set_error("index must be non-null");
         return SPX_E_ARG;
@@ -279,15 +288,6 @@ int check_params(const spx_index* ix, const spc_params* p) {
     }
     return SPX_OK;
 }
-void set_params(ChainArgs& a, const spc_params& p) {
-    a.lookback = p.lookback;
-    a.max_dist = p.max_dist;
-    a.max_gap = p.max_gap;
-    a.gap_penalty = p.gap_penalty;
-}
-
-}  // namespace
-
 void release_chain(spx_index* ix) {
     for (auto& sc : ix->chain_scr)
         if (sc.p) (void)hipFree(sc.p);
@@ -303,7 +303,7 @@ extern "C" {
 int spc_chain_device(spx_index* ix, const spm_match* d_matches, const uint32_t* d_match_docs, const uint64_t* d_match_offsets,
                      uint64_t nreads, const spc_params* params, spc_chain* d_out, uint32_t* d_out_score, uint32_t* d_out_pred,
                      void* stream) {
-    int rc = check_params(ix, params);
+    int rc = chain_check_params(ix, params);
     if (rc != SPX_OK) return rc;
     if (nreads && (!d_matches || !d_match_offsets || !d_out)) {
         set_error("d_matches, d_match_offsets and d_out must be non-null");
@@ -360,7 +360,7 @@ int spc_chain_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
         set_error("no HIP device visible: the chains are computed on the GPU and there is no CPU fallback");
         return SPX_E_NODEVICE;
     }
-    int rc = check_params(ix, params);
+    int rc = chain_check_params(ix, params);
     if (rc != SPX_OK) return rc;
     if (min_length == 0) {
         set_error("min_length must be at least 1: a position of length 0 matches nothing");
@@ -398,7 +398,7 @@ int spc_chain_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
     std::vector<uint64_t> match_offsets(nreads + 1);
     uint64_t n = 0;
     rc = mems_begin_staged(ix, digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, match_offsets.data(), out_values, &n,
-                           [&](const MemsOnDevice& m) -> int {
+                           false, [&](const MemsOnDevice& m) -> int {
                                ChainArgs a{};
                                a.M = (const uint4*)m.records;
                                a.D = m.docs;

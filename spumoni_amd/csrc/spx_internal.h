@@ -162,6 +162,8 @@ struct BatchArgs {
 
 }  // namespace spx
 
+struct spc_params;  // include/spumoni_chain.h
+
 namespace spx {
 // The device arrays of an index once more than one handle uses them: spx_index_clone onto the SAME device hands out a
 // second query context -- its own counters, scratch, stream and locks -- over the same (read-only) arrays instead of a
@@ -302,6 +304,15 @@ struct spx_index {
     enum { H_OUT, H_COUNT };
     Scratch chain_scr[H_COUNT];
     Product chain;  // acc: reads, anchors, chained reads, chain anchors, candidates
+    // alignments (spx_align.hip): the gap counts, their offsets, the per-gap table, where each gap's strings start, the list
+    // of the gaps that take a wavefront and the scan's space (under mu), then spa_align_batch's chain records, its
+    // alignments and pred (under host_mu); the events between the four steps of the last call and their times
+    enum { L_CNT, L_GOFFS, L_GAPS, L_DESC, L_LIST, L_CUB, L_CHAINS, L_OUT, L_PRED, L_COUNT };
+    Scratch align_scr[L_COUNT];
+    Product align;  // acc: reads, aligned reads, gaps, filled gaps, cells
+    hipEvent_t ev_align[3] = {nullptr, nullptr, nullptr};
+    bool align_steps = false;
+    float align_step_ms[4] = {};
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -431,12 +442,20 @@ void release_mems(spx_index* ix);
 void release_place(spx_index* ix);
 // spx_chain.hip: the same for the chains
 void release_chain(spx_index* ix);
+// spx_chain.hip: the chain parameters' ranges (SPX_E_ARG with a message beyond them)
+int chain_check_params(const spx_index* ix, const struct ::spc_params* p);
+// spx_align.hip: the same for the alignments
+void release_align(spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on
 // m.stream; the call returns when that stream has been waited for.  The records stay in mems_scr (M_MOFFS, M_OUT,
 // M_OUT_DOCS) as they do for spm_mems_fetch.  The caller holds host_mu, has set the device and passes nreads >= 1.
+// reads_characters: `then` reads the piece's characters (MemsOnDevice::reads at read_offsets: the digested reads under
+// digestion), so they are not parked while the call runs (StageJob::reads_characters).
 struct MemsOnDevice {
+    const uint8_t* reads;           // the characters the walk saw
+    const uint64_t* read_offsets;   // nreads + 1
     const uint64_t* match_offsets;  // nreads + 1
     const void* records;            // n spm_match
     const uint32_t* docs;           // n ids, null unless asked for
@@ -445,7 +464,7 @@ struct MemsOnDevice {
 };
 int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
                       uint64_t nreads, uint64_t min_length, int want_docs, uint64_t* match_offsets, uint64_t* out_values,
-                      uint64_t* n_matches, const std::function<int(const MemsOnDevice&)>& then);
+                      uint64_t* n_matches, bool reads_characters, const std::function<int(const MemsOnDevice&)>& then);
 // spx_flatten.hip: (re)builds fat / fat_js from letters, Q, dirrows and aux (view.r / nfat / fat_stride set)
 int build_fat(spx_index* ix);
 // spx_walk.hip: MS text against the index: text[samples_start[k]] must be the head of run k

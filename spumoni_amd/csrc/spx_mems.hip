@@ -430,7 +430,7 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
         return SPX_OK;
     }
     return mems_begin_staged(ix, digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, match_offsets, out_values,
-                             n_matches, {});
+                             n_matches, false, {});
 }
 
 }  // extern "C"
@@ -439,7 +439,7 @@ namespace spx {
 
 int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
                       uint64_t nreads, uint64_t min_length, int want_docs, uint64_t* match_offsets, uint64_t* out_values,
-                      uint64_t* n_matches, const std::function<int(const MemsOnDevice&)>& then) {
+                      uint64_t* n_matches, bool reads_characters, const std::function<int(const MemsOnDevice&)>& then) {
     mems_reset(ix);
     *n_matches = 0;
     match_offsets[0] = 0;
@@ -455,6 +455,7 @@ int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, co
     job.out_values = out_values;
     job.want_docs = want_docs != 0;
     job.one_piece = true;
+    job.reads_characters = reads_characters;
     int rc;
     if ((rc = ctx_stream_of(ix, &job.streams[0])) != SPX_OK) return rc;
     hipStream_t st = job.streams[0];
@@ -490,7 +491,7 @@ int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, co
         a.cap = n;
         if ((r = mems_enqueue_write(ix, a, v.value_bits, st)) != SPX_OK) return r;
         ix->mems_pending = true;
-        if (then && (r = then(MemsOnDevice{(const uint64_t*)d_moffs, d_out, (const uint32_t*)d_out_docs, nreads, n, st})) != SPX_OK)
+        if (then && (r = then(MemsOnDevice{v.reads, v.offs, (const uint64_t*)d_moffs, d_out, (const uint32_t*)d_out_docs, nreads, n, st})) != SPX_OK)
             return r;
         if ((r = mems_collect(ix)) != SPX_OK) return r;
         if (then && (r = ctx_wait(ix, st)) != SPX_OK) return r;
