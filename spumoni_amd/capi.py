@@ -725,6 +725,73 @@ class Index:
         out["step_ms"] = list(s.step_ms)
         return out
 
+    # -- CIGARs (include/spumoni_cigar.h) -------------------------------------------
+    def cigar_device(self, d_reads, d_read_offsets, d_matches, d_match_offsets, d_chains, d_pred, params=None, gap_capacity=None,
+                     op_capacity=None, d_out=None, d_out_op_offsets=None, d_out_ops=None, stream=None):
+        """align_device's records and, beside them, each read's path as merged entries (length << 4 | op, cigar.py) from the
+        same inputs.  Returns (d_out int32 (reads, 12), d_out_op_offsets int64[reads + 1], d_out_ops int32[op_capacity]);
+        gap_capacity defaults to the number of matches, which always suffices, op_capacity to the number of read
+        characters plus twice the matches plus the reads, which suffices unless gaps of the text go unfilled in runs.
+        params: (max_fill,) or None for the default."""
+        import torch
+
+        from .align import AlignParams
+
+        L = _spg()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = d_match_offsets.device
+        nreads = d_match_offsets.numel() - 1
+        if gap_capacity is None:
+            gap_capacity = d_matches.numel() // 4
+        if op_capacity is None:
+            op_capacity = 2 * d_reads.numel() + 2 * (d_matches.numel() // 4) + max(nreads, 0)
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 12), dtype=torch.int32, device=dev)
+        if d_out_op_offsets is None:
+            d_out_op_offsets = torch.empty(max(nreads, 0) + 1, dtype=torch.int64, device=dev)
+        if d_out_ops is None:
+            d_out_ops = torch.empty(max(int(op_capacity), 1), dtype=torch.int32, device=dev)
+        p = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        _check(L.spg_cigar_device(self._h, _t_ptr(d_reads), _t_ptr(d_read_offsets), _t_ptr(d_matches), _t_ptr(d_match_offsets), nreads,
+                                  _t_ptr(d_chains), _t_ptr(d_pred), C.byref(p), int(gap_capacity), int(op_capacity), _t_ptr(d_out),
+                                  _t_ptr(d_out_op_offsets), _t_ptr(d_out_ops), C.c_void_p(st.cuda_stream)))
+        return d_out, d_out_op_offsets, d_out_ops
+
+    def cigar_host(self, seqs, offs, min_length, chain_params=None, params=None, digest=None, want_docs=False):
+        """spg_cigar_begin + spg_cigar_fetch: reads in, (records align.ALIGN_DTYPE[reads], op_offsets uint64[reads + 1],
+        entries uint32[op_offsets[-1]], chains chain.CHAIN_DTYPE[reads], values uint64[reads]) out.  digest: (kind, k, w)
+        or None."""
+        from .align import ALIGN_DTYPE, AlignParams
+        from .chain import CHAIN_DTYPE, ChainParams
+
+        L = _spg()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=ALIGN_DTYPE)
+        chains = np.zeros(max(nreads, 1), dtype=CHAIN_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        n = C.c_uint64(0)
+        _check(L.spg_cigar_begin(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                 C.byref(cp), C.byref(ap), _np_ptr(rec), _np_ptr(chains), _np_ptr(vals), C.byref(n)))
+        op_offsets = np.zeros(max(nreads, 0) + 1, dtype=np.uint64)
+        ops = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(L.spg_cigar_fetch(self._h, _np_ptr(op_offsets), _np_ptr(ops)))
+        return rec[:nreads], op_offsets, ops[:n.value], chains[:nreads], vals[:nreads]
+
+    def cigar_stats(self) -> dict:
+        """Of the most recent cigar_device / cigar_host call: align_stats' counts, the entries, the words of path, the error and
+        overflow flags, kernel time, the time of the five steps (plan, lane fills, wavefront fills with their walk back,
+        emit, reduce) and the wavefronts' ticks of fill and walk back."""
+        s = SpgCigarStats()
+        _check(_spg().spg_last_cigar_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpgCigarStats._fields_}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -914,6 +981,35 @@ def _spa() -> C.CDLL:
         L.spa_align_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams), vp, vp, vp]
         L.spa_last_align_stats.argtypes = [vp, C.POINTER(SpaAlignStats)]
         _SPA_READY = True
+    return L
+
+
+# ---- the CIGARs (include/spumoni_cigar.h) ---------------------------------------------------------------------------
+CIGAR_EXPORTS = ["spg_cigar_device", "spg_cigar_begin", "spg_cigar_fetch", "spg_last_cigar_stats"]
+_SPG_READY = False
+
+
+class SpgCigarStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("aligned_reads", C.c_uint64), ("gaps", C.c_uint64), ("filled_gaps", C.c_uint64),
+                ("cells", C.c_uint64), ("entries", C.c_uint64), ("path_words", C.c_uint64), ("wave_fill_ticks", C.c_uint64),
+                ("wave_back_ticks", C.c_uint64), ("error", C.c_uint32), ("overflow", C.c_uint32), ("kernel_ms", C.c_float),
+                ("step_ms", C.c_float * 5)]
+
+
+def _spg() -> C.CDLL:
+    """The library with the spg_* argtypes set (on first use)."""
+    global _SPG_READY
+    L = lib()
+    if not hasattr(L, "spg_cigar_begin"):
+        raise SpxError(f"{LIB_PATH} has no cigar kernels (spg_cigar_begin): there is no CPU fallback")
+    if not _SPG_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spg_cigar_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, C.POINTER(SpaParams), u64, u64, vp, vp, vp, vp]
+        L.spg_cigar_begin.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams), vp, vp, vp,
+                                      C.POINTER(u64)]
+        L.spg_cigar_fetch.argtypes = [vp, vp, vp]
+        L.spg_last_cigar_stats.argtypes = [vp, C.POINTER(SpgCigarStats)]
+        _SPG_READY = True
     return L
 
 

@@ -1,0 +1,153 @@
+// cigar_main.cpp -- `spumoni cigar`: one line per read -- `spumoni align`'s columns and, behind them, the alignment's path
+// as a CIGAR: where the matches (=), substitutions (X), insertions (I) and deletions (D) are, and the text skipped by a
+// gap too large to fill (N) (include/spumoni_cigar.h has the rule).  The reads come from reads.cpp (same ids, same FASTA /
+// FASTQ quirks as `run`), the MS index through the loaders `run` uses, and super-batches of SPUMONI_SUPER_BATCH characters
+// go through spg_cigar_begin / spg_cigar_fetch: digestion, walk, extension, the matches, the chaining, the tables and
+// their walk back stay on the device; 48 bytes per read and four bytes per entry come back.  The driver is
+// read_command.cpp; a run that fails leaves no file.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../../include/spumoni_cigar.h"
+#include "read_command.hpp"
+
+using namespace spumoni_host;
+
+namespace {
+
+int spumoni_cigar_usage() {
+    std::fprintf(stderr, "spumoni cigar - Uses a spumoni MS index to align each read along the best chain of its matches with the reference and reports the alignment's path as a CIGAR.\n");
+    std::fprintf(stderr, "Usage: spumoni cigar [options]\n\n");
+    std::fprintf(stderr, "Options:\n");
+    std::fprintf(stderr, "\t%-35sprints this usage message\n", "-h, --help");
+    std::fprintf(stderr, "\t%-25s%-10soutput prefix used for index\n", "-r, --ref", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10spath to patterns file that will be used.\n", "-p, --pattern", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10sturn off minimizer digestion of reads (default: on)\n", "-n, --no-digest", "");
+    std::fprintf(stderr, "\t%-25s%-10suse alphabet-promoted minimizers\n", "-m, --minimizer-alphabet", "");
+    std::fprintf(stderr, "\t%-25s%-10suse DNA-letter based minimizers\n", "-a, --dna-minimizer", "");
+    std::fprintf(stderr, "\t%-25s%-10ssmall window size (k) for finding minimizers (default: 4)\n", "-K, --small-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10slarge window size (w) for finding minimizers (default: 11)\n", "-W, --large-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10suse document array: matches chain within one document, and the alignment names it\n", "-d, --doc-array", "");
+    std::fprintf(stderr, "\t%-25s%-10sa match is an anchor when it is at least this long, 1 or more (default: the\n", "-L, --min-length", "[INT]");
+    std::fprintf(stderr, "\t%-35sMS threshold `run -c` classifies with, from the null database)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest distance between two chained anchors in the read and in the text,\n", "-S, --max-dist", "[INT]");
+    std::fprintf(stderr, "\t%-35s1 .. 2147483647 (default: 5000)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest difference of those two distances, 0 .. 2147483647 (default: 500)\n", "-G, --max-gap", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat a unit of that difference costs, 0 .. 65535 (default: 1)\n", "-B, --gap-penalty", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10spredecessors an anchor looks back at, 1 .. 64 (default: 64)\n", "-H, --lookback", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10sa gap between two anchors is filled when neither side is longer, 1 .. 4096\n", "-F, --max-fill", "[INT]");
+    std::fprintf(stderr, "\t%-35s(default: 512)\n\n", "");
+    std::fprintf(stderr, "Matching statistics (-M) are implied. Writes <pattern>.cigars: id, values, read_start, read_end, ref_start,\n");
+    std::fprintf(stderr, "ref_end, matches, edits, anchors, unfilled, skipped[, doc] and the CIGAR per read, positions in the (digested) read\n");
+    std::fprintf(stderr, "and text; the CIGAR's operations are = X I D and, for the text side of a gap that is not filled, N; a run is at\n");
+    std::fprintf(stderr, "most 268435455 long and a longer one is printed as several. A read without a match has -1 for ref_start (and doc),\n");
+    std::fprintf(stderr, "zeros elsewhere and * for the CIGAR.\n\n");
+    return 1;
+}
+
+}  // namespace
+
+int cigar_main(int argc, char** argv) {
+    if (argc == 1) return spumoni_cigar_usage();
+    ReadOptions o;
+    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
+    parse_read_options(argc, argv, o, spumoni_cigar_usage, true, "L:S:G:B:H:F:",
+                       {{"min-length", required_argument, NULL, 'L'},
+                        {"max-dist", required_argument, NULL, 'S'},
+                        {"max-gap", required_argument, NULL, 'G'},
+                        {"gap-penalty", required_argument, NULL, 'B'},
+                        {"lookback", required_argument, NULL, 'H'},
+                        {"max-fill", required_argument, NULL, 'F'}},
+                       [&](int c, const char* arg) {
+                           if (c == 'L') {
+                               o.have_threshold = true;
+                               o.threshold = std::strtoull(arg, nullptr, 10);
+                           } else {
+                               (c == 'S' ? max_dist : c == 'G' ? max_gap : c == 'B' ? gap_penalty : c == 'H' ? lookback : max_fill) =
+                                   arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
+                           }
+                       });
+    require_ref_and_pattern(o);
+    if (o.pml_requested)
+        fatal_warning("-P cannot be used with `spumoni cigar`: the anchors are read off matching statistics (-M is implied); "
+                      "PMLs have no pointers.");
+    o.ms = true;
+    validate_read_options(o);
+    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
+    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
+    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
+    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
+    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
+    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
+    o.ref_file += o.use_promotions ? ".bin" : ".fa";
+    const std::vector<void*> entry = device_entry_points("cigar", {"spg_cigar_begin", "spg_cigar_fetch"}, "the cigar kernels");
+    auto cigar_begin = reinterpret_cast<decltype(&spg_cigar_begin)>(entry[0]);
+    auto cigar_fetch = reinterpret_cast<decltype(&spg_cigar_fetch)>(entry[1]);
+    ReadRun run;
+    open_read_run(o, 8u << 20, run);
+    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spg_cigar_begin)
+    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
+    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
+    const spa_params fill{(uint32_t)max_fill};
+    std::fprintf(stderr, "[cigar] index loaded (n = %llu, r = %llu); a match is an anchor from length %llu on (max-dist %llu, max-gap %llu, "
+                 "gap penalty %llu, lookback %llu, max-fill %llu)\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)min_length, max_dist, max_gap,
+                 gap_penalty, lookback, max_fill);
+
+    LinesFile out;
+    out.open(o.pattern_file + ".cigars", false);
+    uint64_t num_reads = 0, num_aligned = 0, num_entries = 0;
+    std::vector<spa_alignment> recs;
+    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
+    std::vector<uint32_t> ops;
+    static const char op_char[16] = {'?', 'I', 'D', 'N', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    scan_reads(
+        run, out,
+        [&](ReadBatch& b) {
+            recs.resize(b.take + 1);
+            op_offs.assign(b.take + 1, 0);
+            ops.clear();
+            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
+            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
+                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+                uint64_t n = 0;
+                if (cigar_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
+                                min_length, o.use_doc ? 1 : 0, &params, &fill, recs.data() + q0, nullptr, b.values.data() + q0,
+                                &n) != SPX_OK)
+                    fatal_error("%s", spx_last_error());
+                const size_t at = ops.size();
+                ops.resize(at + n + 1);
+                piece_offs.resize(q1 - q0 + 1);
+                if (cigar_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
+                ops.resize(at + n);
+                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
+            }
+        },
+        [&](const ReadBatch& b, size_t i) {
+            const spa_alignment& c = recs[i];
+            const bool aligned = c.ref_start != SPA_UNALIGNED;
+            std::fwrite(b.recs[i].id, 1, b.recs[i].id_len, out.f);
+            std::fprintf(out.f, "\t%llu\t%u\t%u\t", (unsigned long long)b.values[i], c.read_start, c.read_end);
+            if (aligned)
+                std::fprintf(out.f, "%llu", (unsigned long long)c.ref_start);
+            else
+                std::fputs("-1", out.f);
+            std::fprintf(out.f, "\t%llu\t%u\t%u\t%u\t%u\t%u", (unsigned long long)c.ref_end, c.matches, c.edits, c.anchors, c.unfilled,
+                         c.skipped);
+            if (o.use_doc) std::fprintf(out.f, "\t%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
+            std::fputc('\t', out.f);
+            if (op_offs[i] == op_offs[i + 1]) std::fputc('*', out.f);
+            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e) std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
+            std::fputc('\n', out.f);
+            num_entries += op_offs[i + 1] - op_offs[i];
+            num_aligned += aligned;
+            num_reads++;
+        });
+    std::fprintf(stderr, "[cigar] %llu reads, %llu aligned, %llu without a match, %llu CIGAR entries (%.3f sec). results are saved in *.cigars\n",
+                 (unsigned long long)num_reads, (unsigned long long)num_aligned, (unsigned long long)(num_reads - num_aligned),
+                 (unsigned long long)num_entries, std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count());
+    return 0;
+}

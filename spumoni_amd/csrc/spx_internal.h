@@ -313,6 +313,22 @@ struct spx_index {
     hipEvent_t ev_align[3] = {nullptr, nullptr, nullptr};
     bool align_steps = false;
     float align_step_ms[4] = {};
+    // CIGARs (spx_cigar.hip): the scratch of the shared count, walk and reduce as above, the list of the gaps that take a
+    // wavefront (two kinds, from either end), each gap's words of path and their offsets, the path, the wavefronts' trace
+    // buffers and the reads' entry counts (under mu), then spg_cigar_begin's chain records, alignments, pred, op offsets
+    // and entries (under host_mu); the events around the steps of the last call and their times; what the counters hold
+    // beyond Product::acc (path words, the bound of the entries, the ticks of fill and walk back); and the entries that
+    // wait for spg_cigar_fetch
+    enum { TB_CNT, TB_GOFFS, TB_GAPS, TB_DESC, TB_LIST, TB_CUB, TB_PW, TB_POFFS, TB_PATH, TB_TRACE, TB_OCNT, TB_CHAINS, TB_OUT,
+           TB_PRED, TB_OOFFS, TB_OPS, TB_COUNT };
+    Scratch cigar_scr[TB_COUNT];
+    Product cigar;  // acc: reads, aligned reads, gaps, filled gaps, cells, entries
+    hipEvent_t ev_cigar[7] = {};
+    bool cigar_phase[2] = {false, false};  // the events of the plan / of the other steps were recorded by the last call
+    float cigar_step_ms[5] = {};
+    uint64_t cigar_extra[4] = {};
+    bool cigar_ready = false;
+    uint64_t cigar_ready_n = 0, cigar_ready_reads = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -446,6 +462,8 @@ void release_chain(spx_index* ix);
 int chain_check_params(const spx_index* ix, const struct ::spc_params* p);
 // spx_align.hip: the same for the alignments
 void release_align(spx_index* ix);
+// spx_cigar.hip: the same for the CIGARs
+void release_cigar(spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on
