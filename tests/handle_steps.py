@@ -29,9 +29,16 @@ import numpy as np
 import torch
 
 from spumoni_amd import capi, synth
+from spumoni_amd.align import ALIGN_DTYPE, GAP_DTYPE, UNALIGNED, UNFILLED, AlignParams, align_reference
+from spumoni_amd.chain import CHAIN_DTYPE, NO_DOC, chain_reference
+from spumoni_amd.cigar import OP_D, OP_EQ, OP_I, cigar_reference
 from spumoni_amd.docvote import VOTE_DTYPE, votes_reference
 from spumoni_amd.mems import MATCH_DTYPE, mems_reference
+from spumoni_amd.place import PLACEMENT_DTYPE, UNPLACED, place_reference
 from tests import cases
+from tests import grid_cases as gc
+from tests.test_gpu_align import Batch
+from tests.test_gpu_place import _to_device
 from tests.text_lines import _expect, _fill
 
 PML, MS = capi.SPX_MODE_PML, capi.SPX_MODE_MS
@@ -40,7 +47,7 @@ N = ord("N")
 FENCE = 64  # bytes of PATTERN on either side
 PATTERN = 0xA5
 K, W = 4, 11  # the digestion's (k, w)
-N_STEPS = 51  # steps of the catalogue (the tests are parametrised over it before anything is built; build() must give as many)
+N_STEPS = 61  # steps of the catalogue (the tests are parametrised over it before anything is built; build() must give as many)
 OPTION_DEFAULTS = {"chunk_mode": 0, "chunk_shift": 0, "chunk_len": 0, "digest_kernel": 0, "digest_parked": 0}
 
 # step family                          dirtier                                        the scratch they share; what the dirtier leaves there
@@ -59,6 +66,18 @@ OPTION_DEFAULTS = {"chunk_mode": 0, "chunk_shift": 0, "chunk_len": 0, "digest_ke
 # matches, one start per read          every position a start                         mems_scr[] M_BITS / M_PREFIX: a bitmap of ones
 # text of 1-digit values               MS pointers of 13 digits, four times the size  S_LINE_BYTES .. S_TEXT: longer lines
 # class records, every bin below       threshold 0 on more reads                      S_CLASS: every bin above
+# placements, 16 bit, short reads      32 bit with reads above 2 048 values           the product's counters; the 16-lane path behind the whole-wavefront one
+# place_host                           place_host on a read of 70 000 characters      place_scr[], stage_scr[]: 32-bit values of six times the characters
+# chains with f and pred, <= 16        reads of 5 000 anchors with ids                the counters; the ring of 64 before the groups of 16 lanes
+# chain_host                           chain_host at min_length 1 on noisier reads    M_OUT, M_MOFFS of mems_scr[], H_OUT of chain_scr[], stage_scr[]: four times the matches
+# align_device, table in caller        every gap wave-sized and filled, four times    align_scr[] L_DESC, L_LIST: descriptors and a list full of other offsets
+# buffers / in the scratch, capacity   the gaps                                       L_GAPS: the places of the read that does not fit must not keep the
+# one short inside a middle read                                                      dirtier's sides
+# align_host                           align_host on reads with ten times the edits   L_CHAINS, L_PRED, L_OUT
+# cigar_device at max_fill 512,        max_fill 4 096, 20 traces in device memory     cigar_scr[] TB_TRACE at another stride, TB_PATH full of codes 2 and 3,
+# nearly all '='; op_capacity short    (16 wavefronts), lopsided and empty-sided      TB_LIST filled from both ends; TB_OCNT, TB_POFFS: the read that does not
+# of the last read                     gaps                                           fit comes back unaligned
+# cigar_host                           cigar_host on reads with ten times the edits   TB_OOFFS, TB_OPS between spg_cigar_begin and spg_cigar_fetch
 
 
 class Mismatch(AssertionError):
@@ -578,6 +597,302 @@ class Mems(Family):
         assert st["matches"] == n and st["written"] == n and st["values"] == step.chars, (self.name, st, n)
 
 
+class Product(Family):
+    """What Place, Chain, Align and Cigar share: expect(k) computed once per k, the oracle's MS arrays of a host form's batch
+    and the matches mems_reference makes of them (the library's own matches never enter an expectation)."""
+
+    def __init__(self, cat, name, index, nreads, form, batch=None, min_length=0):
+        super().__init__(name, index, nreads)
+        self.cat, self.form, self.batch, self.min_length = cat, form, batch, min_length
+        self._memo, self.seen = {}, {}
+        self.ms = cat.oracle_values(index, batch, MS) if form == "host" else None
+
+    def text(self):
+        return self.cat.indexes[self.index]["text"]
+
+    def expect(self, k):
+        if k not in self._memo:
+            self._memo[k] = self.compute(k)
+        return self._memo[k]
+
+    def host_reads(self, k):
+        offs = np.asarray(self.batch[1][: k + 1], dtype=np.uint64)
+        return self.batch[0][: int(offs[-1])], offs
+
+    def matches(self, k):
+        """(match_offsets, records) of the batch's first k reads"""
+        m = mems_reference(self.ms["lengths"], self.ms["pointers"], np.asarray(self.batch[1][: k + 1], dtype=np.int64), self.min_length)
+        return m[0], m[1]
+
+    def host_job(self, call, keys):
+        res = {}
+
+        def launch(ix, stream):
+            set_options(ix, {})
+            res.update(zip(keys, call(ix)))
+
+        return Job(launch, lambda: res)
+
+
+def _pattern_behind(fence_values, written, what):
+    """the places of a fenced output that the capacity covers and the call must leave alone"""
+    tail = fence_values[written:].view(np.uint8)
+    if (tail != PATTERN).any():
+        raise Mismatch(f"{what}: written behind the {written} values that fit")
+    return fence_values[:written]
+
+
+class Place(Product):
+    """spp_place_device over uploaded arrays (crafted: the rule is one on the arrays and the text), spp_place_batch (form
+    host) against place_reference over the oracle's MS lengths and pointers."""
+
+    def __init__(self, cat, name, index, offs, R, L, P, D, bits, params, form="device", batch=None):
+        super().__init__(cat, name, index, len(offs) - 1, form, batch)
+        self.offs, self.R, self.L, self.P, self.D, self.bits, self.params = np.asarray(offs, dtype=np.int64), R, L, P, D, bits, params
+        if form == "host":
+            self.R, self.L, self.P = batch[0], self.ms["lengths"], self.ms["pointers"]
+        assert int(np.max(self.L, initial=0)) < (1 << bits) and (D is None or int(np.max(D, initial=0)) < (1 << bits))
+
+    def compute(self, k):
+        offs = self.offs[: k + 1]
+        want = {"records": place_reference(self.R, self.L, self.P, offs.astype(np.uint64), self.text(), *self.params, docs=self.D)}
+        if self.form == "host":
+            want["values"] = np.diff(offs).astype(np.uint64)
+        return int(offs[-1] - offs[0]), want
+
+    def prepare(self, k):
+        if self.form == "host":
+            seqs, offs = self.host_reads(k)
+            return self.host_job(lambda ix: ix.place_host(seqs, offs, *self.params), ("records", "values"))
+        offs = self.offs[: k + 1]
+        hi = int(offs[-1])
+        d_R, d_L, d_P = _to_device(self.R[:hi], 8), _to_device(self.L[:hi], self.bits), _to_device(self.P[:hi], 64)
+        d_D = None if self.D is None else _to_device(self.D[:hi], self.bits)
+        d_offs = _to_device(offs, 64)
+        fo = DeviceFence(self.name + " records", 8 * k, torch.int32)
+
+        def launch(ix, stream):
+            ix.place_device(d_R, d_L, d_P, d_offs, *self.params, d_docs=d_D, d_out=fo.t, total_values=hi, stream=stream)
+
+        return Job(launch, lambda: {"records": fo.values(np.uint32).view(PLACEMENT_DTYPE).reshape(-1)})
+
+    def path(self, ix, step):
+        st = ix.place_stats()
+        placed = int((step.want["records"]["ref_start"] != np.uint64(UNPLACED)).sum())
+        assert st["values"] == step.chars and st["placed"] == placed, (self.name, st, placed)
+
+
+class Chain(Product):
+    """spc_chain_device over uploaded records (crafted anchors: the rule is one on the records) with f and pred of every
+    anchor; spc_chain_batch (form host) against chain_reference over mems_reference over the oracle's MS arrays."""
+
+    def __init__(self, cat, name, index, offs, rec, D, params=None, form="device", batch=None, min_length=0):
+        nreads = len(batch[1]) - 1 if form == "host" else len(offs) - 1
+        super().__init__(cat, name, index, nreads, form, batch, min_length)
+        self.offs, self.rec, self.D, self.params = None if offs is None else np.asarray(offs, dtype=np.int64), rec, D, params
+
+    def compute(self, k):
+        if self.form == "host":
+            mo, rec = self.matches(k)
+            count = [0]
+            chains, _, _ = chain_reference(mo, rec, self.params, count=count)
+            self.seen[k] = dict(anchors=rec.size, candidates=count[0])
+            return int(self.batch[1][k]), {"records": chains, "values": np.diff(self.batch[1][: k + 1]).astype(np.uint64)}
+        offs = self.offs[: k + 1]
+        lo, hi = int(offs[0]), int(offs[-1])
+        count = [0]
+        chains, score, pred = chain_reference(offs.astype(np.uint64), self.rec, self.params, self.D, count=count)
+        self.seen[k] = dict(anchors=hi - lo, candidates=count[0])
+        return hi - lo, {"records": chains, "score": score[lo:hi], "pred": pred[lo:hi]}
+
+    def prepare(self, k):
+        if self.form == "host":
+            seqs, offs = self.host_reads(k)
+            return self.host_job(lambda ix: ix.chain_host(seqs, offs, self.min_length, self.params), ("records", "values"))
+        offs = self.offs[: k + 1]
+        lo, hi = int(offs[0]), int(offs[-1])
+        d_rec = torch.from_numpy(np.concatenate([self.rec[:hi], np.zeros(1, dtype=MATCH_DTYPE)]).view(np.int32).reshape(-1, 4).copy()).cuda()
+        d_D = None if self.D is None else _upload(np.r_[self.D[:hi], 0], np.uint32)
+        d_offs = torch.from_numpy(offs.copy()).cuda()
+        fo = DeviceFence(self.name + " records", 12 * k, torch.int32)
+        fs = DeviceFence(self.name + " score", hi, torch.int32, lo)
+        fp = DeviceFence(self.name + " pred", hi, torch.int32, lo)
+
+        def launch(ix, stream):
+            ix.chain_device(d_rec, d_offs, self.params, d_match_docs=d_D, d_out=fo.t, d_out_score=fs.t, d_out_pred=fp.t, stream=stream)
+
+        return Job(launch, lambda: {"records": fo.values(np.uint32).view(CHAIN_DTYPE).reshape(-1), "score": fs.values(np.uint32),
+                                    "pred": fp.values(np.uint32)})
+
+    def path(self, ix, step):
+        st, chains, seen = ix.chain_stats(), step.want["records"], self.seen[step.nreads]
+        assert st["reads"] == step.nreads and st["anchors"] == seen["anchors"] and st["candidates"] == seen["candidates"], (self.name, st, seen)
+        assert st["chained_reads"] == int((chains["anchors"] > 0).sum()) and st["chain_anchors"] == int(chains["anchors"].sum()), (self.name, st)
+
+
+UNALIGNED_REC = (UNALIGNED, 0, 0, 0, 0, 0, 0, 0, 0, NO_DOC)
+
+
+class Align(Product):
+    """spa_align_device over crafted reads, anchors, chains and pred (tests/test_gpu_align.py: Batch) on the index's text,
+    the per-gap table in caller buffers or (table False) in the index's scratch; short: a gap capacity one below the end of
+    a middle read's gaps -- that read and every later one with gaps comes back unaligned.  spa_align_batch (form host)
+    against oracle MS -> mems_reference -> chain_reference -> align_reference."""
+    reference = staticmethod(align_reference)
+    TABLE = ("gap_offsets", "gaps")
+
+    def __init__(self, cat, name, index, arrays, params=None, table=True, short=False, form="device", batch=None, min_length=0):
+        nreads = len(batch[1]) - 1 if form == "host" else len(arrays[3]) - 1
+        super().__init__(cat, name, index, nreads, form, batch, min_length)
+        self.arrays, self.params, self.table, self.short = arrays, params, table, short
+
+    def sliced(self, k):
+        R, roffs, rec, moffs, chains, pred = self.arrays
+        return R, roffs[: k + 1], rec, moffs[: k + 1], chains[:k], pred
+
+    def refer(self, k):
+        """(chars, the six arrays, the product's reference over them, align_reference's table, extra keys of a host form)"""
+        if self.form == "host":
+            seqs, offs = self.host_reads(k)
+            mo, rec = self.matches(k)
+            chains, _, pred = chain_reference(mo, rec)
+            arrays, extra = (seqs, offs, rec, mo, chains, pred), {"chains": chains, "values": np.diff(offs.astype(np.int64)).astype(np.uint64)}
+        else:
+            arrays, extra = self.sliced(k), {}
+        R, roffs, rec, moffs, chains, pred = arrays
+        count = [0]
+        table = align_reference(R, roffs, self.text(), moffs, rec, chains, pred, self.params, count=count)
+        ref = table if self.reference is align_reference else self.reference(R, roffs, self.text(), moffs, rec, chains, pred, self.params)
+        return int(roffs[-1]) - int(roffs[0]), arrays, ref, table, count[0], extra
+
+    def gap_capacity(self, k, goffs):
+        if not self.short:
+            return self.arrays[2].size  # the number of records: always enough
+        per_read = np.diff(goffs.astype(np.int64))
+        cand = np.flatnonzero(per_read >= 2)
+        q = int(cand[cand.size // 2])  # a middle read among those with two gaps or more
+        return int(goffs[q + 1]) - 1
+
+    def compute(self, k):
+        chars, arrays, (want, goffs, gaps), _, cells, extra = self.refer(k)
+        self.seen[k] = dict(goffs=goffs, gaps=gaps, cells=cells, cap=None, reference=want)
+        if self.form == "host":
+            return chars, dict(extra, records=want)
+        cap = self.seen[k]["cap"] = self.gap_capacity(k, goffs)
+        fits = (goffs[1:] <= cap) | (np.diff(goffs.astype(np.int64)) == 0)
+        want = want.copy()
+        want[~fits] = UNALIGNED_REC
+        out = {"records": want}
+        if self.table:
+            out.update(gap_offsets=goffs, gaps=gaps)
+        return chars, out
+
+    def uploads(self, k):
+        R, roffs, rec, moffs, chains, pred = self.sliced(k)
+        n = rec.size
+        return (torch.from_numpy(np.r_[R, np.zeros(8, dtype=np.uint8)]).cuda(),
+                torch.from_numpy(np.asarray(roffs, dtype=np.uint64).view(np.int64).copy()).cuda(),
+                torch.from_numpy(np.concatenate([rec, np.zeros(1, dtype=MATCH_DTYPE)]).view(np.int32).reshape(-1, 4).copy()).cuda()[:n],
+                torch.from_numpy(np.asarray(moffs, dtype=np.uint64).view(np.int64).copy()).cuda(),
+                torch.from_numpy(np.concatenate([chains, np.zeros(1, dtype=CHAIN_DTYPE)]).view(np.int32).reshape(-1, 12).copy()).cuda()[:k],
+                torch.from_numpy(np.r_[pred, np.zeros(1, dtype=np.uint32)].view(np.int32).copy()).cuda()[:n])
+
+    def prepare(self, k):
+        if self.form == "host":
+            seqs, offs = self.host_reads(k)
+            return self.host_job(lambda ix: ix.align_host(seqs, offs, self.min_length, None, self.params), ("records", "chains", "values"))
+        self.expect(k)
+        cap, total = self.seen[k]["cap"], self.seen[k]["gaps"].size
+        d = self.uploads(k)
+        fo = DeviceFence(self.name + " records", 12 * k, torch.int32)
+        fg = DeviceFence(self.name + " gap offsets", k + 1, torch.int64) if self.table else None
+        ft = DeviceFence(self.name + " gaps", 4 * cap, torch.int32) if self.table else None
+        p = capi.SpaParams(*(self.params or AlignParams()))
+
+        def launch(ix, stream):
+            st = stream if stream is not None else torch.cuda.current_stream()
+            capi._check(capi._spa().spa_align_device(ix._h, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), k, d[4].data_ptr(),
+                                                     d[5].data_ptr(), capi.C.byref(p), cap, fo.t.data_ptr(), fg.t.data_ptr() if fg else None,
+                                                     ft.t.data_ptr() if ft else None, capi.C.c_void_p(st.cuda_stream)))
+
+        def collect():
+            got = {"records": fo.values(np.uint32).view(ALIGN_DTYPE).reshape(-1)}
+            if self.table:
+                got["gap_offsets"] = fg.values(np.uint64)
+                got["gaps"] = _pattern_behind(ft.values(np.uint32), 4 * min(total, cap), self.name + " gaps").view(GAP_DTYPE).reshape(-1)
+            return got
+
+        return Job(launch, collect)
+
+    def stats(self, ix):
+        return ix.align_stats()
+
+    def path(self, ix, step):
+        st, seen, want = self.stats(ix), self.seen[step.nreads], step.want["records"]
+        ok = int((want["ref_start"] != np.uint64(UNALIGNED)).sum())
+        lost = ok < int((seen["reference"]["ref_start"] != np.uint64(UNALIGNED)).sum())
+        assert st["reads"] == step.nreads and st["aligned_reads"] == ok and st["error"] == 0 and st["overflow"] == int(lost), (self.name, st, ok)
+        assert lost == bool(self.short or getattr(self, "short_ops", False)), (self.name, lost)
+        if not lost:
+            gaps = seen["gaps"]
+            assert st["gaps"] == gaps.size and st["filled_gaps"] == int((gaps["edits"] != UNFILLED).sum()) and st["cells"] == seen["cells"], (self.name, st)
+        return st, lost
+
+
+class Cigar(Align):
+    """spg_cigar_device on the same kind of input, records, op offsets and entries; short_ops: an op capacity one below the
+    entries -- the last read with entries does not fit, writes none and comes back unaligned while the offsets still count
+    it.  spg_cigar_begin + spg_cigar_fetch (form host), the two calls together."""
+    reference = staticmethod(cigar_reference)
+
+    def __init__(self, cat, name, index, arrays, params=None, short_ops=False, form="device", batch=None, min_length=0):
+        super().__init__(cat, name, index, arrays, params, form=form, batch=batch, min_length=min_length)
+        self.short_ops = short_ops
+
+    def compute(self, k):
+        chars, arrays, (want, ooffs, ops), (_, goffs, gaps), cells, extra = self.refer(k)
+        self.seen[k] = dict(goffs=goffs, gaps=gaps, cells=cells, reference=want, ooffs=ooffs, entries=ops.size)
+        if self.form == "host":
+            return chars, dict(extra, records=want, op_offsets=ooffs, entries=ops)
+        R, _, rec, moffs, _, _ = arrays
+        op_cap = int(ooffs[-1]) - 1 if self.short_ops else 2 * R.size + 2 * rec.size + moffs.size + 64
+        fits = ooffs[1:] <= op_cap
+        whole = int(ooffs[1:][fits].max(initial=0))
+        self.seen[k].update(op_cap=op_cap, entries=whole)
+        want = want.copy()
+        want[~fits] = UNALIGNED_REC
+        return chars, {"records": want, "op_offsets": ooffs, "entries": ops[:whole]}
+
+    def prepare(self, k):
+        if self.form == "host":
+            seqs, offs = self.host_reads(k)
+            return self.host_job(lambda ix: ix.cigar_host(seqs, offs, self.min_length, None, self.params),
+                                 ("records", "op_offsets", "entries", "chains", "values"))
+        self.expect(k)
+        op_cap, whole = self.seen[k]["op_cap"], self.seen[k]["entries"]
+        d = self.uploads(k)
+        cap = self.arrays[2].size
+        fo = DeviceFence(self.name + " records", 12 * k, torch.int32)
+        ff = DeviceFence(self.name + " op offsets", k + 1, torch.int64)
+        fe = DeviceFence(self.name + " entries", op_cap, torch.int32)
+
+        def launch(ix, stream):
+            ix.cigar_device(*d, self.params, gap_capacity=cap, op_capacity=op_cap, d_out=fo.t, d_out_op_offsets=ff.t, d_out_ops=fe.t, stream=stream)
+
+        return Job(launch, lambda: {"records": fo.values(np.uint32).view(ALIGN_DTYPE).reshape(-1), "op_offsets": ff.values(np.uint64),
+                                    "entries": _pattern_behind(fe.values(np.uint32), whole, self.name + " entries")})
+
+    def stats(self, ix):
+        return ix.cigar_stats()
+
+    def path(self, ix, step):
+        st, lost = super().path(ix, step)
+        seen = self.seen[step.nreads]
+        assert st["entries"] == seen["entries"], (self.name, st, seen["entries"])
+        if not lost:
+            assert st["path_words"] == gc.path_words(seen["gaps"], (self.params or AlignParams()).max_fill), (self.name, st)
+
+
 # ---- batches -------------------------------------------------------------------------------------------------------------
 def _concat(reads):
     offs = np.concatenate([[0], np.cumsum([r.size for r in reads])]).astype(np.int64)
@@ -665,8 +980,8 @@ class Catalogue:
     def add(self, family, dirtier, claim=None, as_dirtier=False):
         if family.form == "device" and not self.device_forms:
             return
-        if not self.native_only and isinstance(family, (Votes, Mems)):
-            return  # (the stand-in library of the CPU tier has no votes and no matches)
+        if not self.native_only and isinstance(family, (Votes, Mems, Product)):
+            return  # (the stand-in library of the CPU tier has no votes, no matches and none of the products built on them)
         family.dirtier = dirtier
         (self.dirtiers if as_dirtier else self.steps)[family.name] = family.step()
         if claim:
@@ -986,6 +1301,131 @@ def build(oracle_mod, device_forms=True, native_only=True):
     add(Text(cat, "dirty: text with -m digestion on longer reads", m_, dq_long, PML, L_ | D_, digest=(1,)), None, as_dirtier=True)
     add(Text(cat, "query_text PML with -m digestion", m_, dq_reads, PML, L_, digest=(1,)),
         "dirty: text with -m digestion on longer reads", longer_lines)
+    # ---- place, chain, align, cigar: crafted arrays over index 1's text (the kernels read the text alone), and its host batches ----
+    def both(step_family, dirt_family, claim):
+        add(dirt_family, None, as_dirtier=True)
+        add(step_family, dirt_family.name, claim)
+
+    lens16 = np.r_[[0, 1, 2047, 2048, 300], rng.integers(0, 400, size=75)]
+    lens32 = np.r_[[2049, 2500, 5000, 3000, 0], rng.integers(0, 2000, size=80)]
+    p16 = gc.place_batch(rng, text, lens16, np.flatnonzero(lens16 >= 40)[::2], 5)
+    p32 = gc.place_batch(rng, text, lens32, np.flatnonzero(lens32 >= 40)[::2], 0)
+
+    def both_place_paths(step, d):  # reads of up to 2 048 values (a group of 16 lanes), 16 bit, behind reads above that, 32 bit
+        assert int(np.diff(step.family.offs).max()) == 2048 and step.family.bits == 16 and d.family.bits == 32
+        assert int((np.diff(d.family.offs) > 2048).sum()) >= 4
+        for s in (step, d):
+            ok = s.want["records"]["ref_start"] != np.uint64(UNPLACED)
+            assert ok.sum() >= 20 and (~ok).sum() >= 20, s.name
+
+    both(Place(cat, "place_device 16", "real", p16[4], p16[0], p16[1], p16[2], p16[3], 16, (gc.MIN_SEED, 4, 16)),
+         Place(cat, "dirty: place_device 32 with reads above 2 048 values", "real", p32[4], p32[0], p32[1], p32[2], None, 32, (gc.MIN_SEED, 4, 16)),
+         both_place_paths)
+
+    def wide_values(step, d):  # a read of 65 536 values or more is staged in 32 bits; six times the characters
+        assert int(np.diff(step.family.offs).max()) < 65536 <= int(np.diff(d.family.offs).max()) and d.chars >= 6 * step.chars
+        assert (step.want["records"]["ref_start"] != np.uint64(UNPLACED)).sum() >= step.nreads // 2
+
+    both(Place(cat, "place_host", "real", mbatch[1], None, None, None, None, 32, (20, 4, 16), "host", mbatch),
+         Place(cat, "dirty: place_host on a read of 70 000 characters", "real", big_ms[1], None, None, None, None, 32, (20, 4, 16), "host", big_ms),
+         wide_values)
+
+    c16 = gc.chain_batch(rng, rng.integers(0, 17, size=700), front=3)
+    c5000 = gc.chain_batch(rng, [5000] * 6, front=1, n_docs=2)
+
+    def long_path_first(step, d):  # groups of 16 lanes against the whole wavefront with its ring of 64, with ids
+        assert int(np.diff(step.family.offs).max()) == 16 and int(np.diff(d.family.offs).min()) == 5000 and d.family.D is not None
+        assert int(d.want["records"]["anchors"].min()) > 64 and int((step.want["records"]["anchors"] > 1).sum()) > step.nreads // 2
+
+    both(Chain(cat, "chain_device with f and pred", "real", c16[0], c16[1], None),
+         Chain(cat, "dirty: chain_device, reads of 5 000 anchors with ids", "real", c5000[0], c5000[1], c5000[2]), long_path_first)
+
+    def four_times_the_matches(step, d):
+        a, b = step.family.seen[step.nreads]["anchors"], d.family.seen[d.nreads]["anchors"]
+        assert b >= 4 * a > 0 and int((step.want["records"]["anchors"] > 1).sum()) >= 10, (step.name, a, b)
+
+    both(Chain(cat, "chain_host", "real", None, None, None, None, "host", mbatch, 8),
+         Chain(cat, "dirty: chain_host at min_length 1 on noisier reads", "real", None, None, None, None, "host", mmany, 1), four_times_the_matches)
+
+    def crafted_reads(shapes, per_read, empty_every=0, mutate=0.3, front=0):
+        """a Batch over index 1's text: reads of `per_read` gaps each in the order of `shapes` (a shape may carry its read's own
+        share of replaced characters as a third value), an anchor-less read now and then"""
+        B = Batch(front=front)
+        for n_, i in enumerate(range(0, len(shapes), per_read)):
+            mine = [(int(s[0]), int(s[1])) for s in shapes[i:i + per_read]]
+            room = sum(b for _, b in mine) + 12 * (len(mine) + 1)
+            B.add(text, rng, int(rng.integers(0, text.size - room)), mine, mutate=shapes[i][2] if len(shapes[i]) > 2 else mutate)
+            if empty_every and n_ % empty_every == 0:
+                B.add_empty()
+        return B.arrays()
+
+    a_small = crafted_reads(rng.integers(0, 25, size=(260, 2)), 2, empty_every=4, front=2)
+    wave_shapes = gc.SMALL_WAVE * 270 + gc.LARGE_WAVE * 4
+    a_wave = crafted_reads([wave_shapes[i] for i in rng.permutation(len(wave_shapes))], 6)
+
+    def lists_full(step, d):  # every gap of the dirtier is listed for a wavefront and filled: four times the gaps
+        sg, dg = step.family.seen[step.nreads]["gaps"], d.family.seen[d.nreads]["gaps"]
+        assert gc.wave_sized(dg, 512).all() and (dg["edits"] != UNFILLED).all() and dg.size >= 4 * sg.size > 100, (step.name, sg.size, dg.size)
+        assert min(int(gc.wave_sized(sg, 512).sum()), int((~gc.wave_sized(sg, 512)).sum())) >= 50  # the step has gaps for a lane, too
+
+    def one_short_in_the_middle(step, d):
+        lists_full(step, d)
+        seen = step.family.seen[step.nreads]
+        q = int(np.searchsorted(seen["goffs"], seen["cap"], side="right")) - 1  # the read the capacity ends in
+        assert int(seen["goffs"][q]) < seen["cap"] == int(seen["goffs"][q + 1]) - 1 and step.nreads // 4 < q < 3 * step.nreads // 4
+        lost = (step.want["records"]["ref_start"] == np.uint64(UNALIGNED)) & (seen["reference"]["ref_start"] != np.uint64(UNALIGNED))
+        assert lost[q] and not lost[:q].any() and lost.sum() >= 10
+
+    add(Align(cat, "dirty: align_device, every gap wave-sized and filled", "real", a_wave), None, as_dirtier=True)
+    add(Align(cat, "align_device, table in caller buffers", "real", a_small), "dirty: align_device, every gap wave-sized and filled", lists_full)
+    add(Align(cat, "align_device, table in the scratch, capacity one short in a middle read", "real", a_small, table=False, short=True),
+        "dirty: align_device, every gap wave-sized and filled", one_short_in_the_middle)
+
+    def ten_times_the_edits(step, d):
+        a, b = int(step.want["records"]["edits"].sum()), int(d.want["records"]["edits"].sum())
+        assert b >= 10 * a > 0 and (step.want["records"]["anchors"] > 1).sum() >= 10, (step.name, a, b)
+
+    both(Align(cat, "align_host", "real", None, form="host", batch=mbatch, min_length=8),
+         Align(cat, "dirty: align_host on reads with ten times the edits", "real", None, form="host", batch=mmany, min_length=6), ten_times_the_edits)
+
+    equal = [(3, 3), (17, 17), (20, 20), (40, 40), (1, 1), (64, 64), (2, 2), (33, 33)] * 14
+    equal[20:20] = [(300, 300), (5, 5)]  # two traces in device memory, all '=' too
+    equal[90:90] = [(300, 300), (18, 18)]
+    equal[50:50] = [(6, 7, 0.3), (20, 18), (3, 3, 0.3), (17, 30)]  # the few reads with edits
+    g_step = crafted_reads(equal, 2, empty_every=5, mutate=0.0)
+    lopsided = [(1100, 17), (17, 1100), (200, 0), (0, 200)] * 10 + [(1100, 17)] * 10 + [(1, 300), (300, 1), (150, 0)] * 4
+    g_dirty = crafted_reads([lopsided[i] for i in rng.permutation(len(lopsided))], 3, mutate=0.5)
+
+    def op_lengths(step):
+        e = step.want["entries"]
+        return {op: int((e[(e & 15) == op] >> 4).sum()) for op in (OP_EQ, OP_I, OP_D)}, int((e >> 4).sum())
+
+    def other_stride(step, d):  # nearly all '=' at max_fill 512 behind paths of 'I' and 'D' at max_fill 4 096 with 20 traces in device memory
+        sg, dg = step.family.seen[step.nreads]["gaps"], d.family.seen[d.nreads]["gaps"]
+        assert step.family.params is None and d.family.params == AlignParams(4096)
+        far = gc.wave_sized(dg, 4096) & (gc.trace_words(dg) > gc.TRACE_LDS_WORDS)
+        assert int(far.sum()) >= 17 > gc.grid_global(4096, d.family.arrays[2].size) == 16 and (dg["edits"] != UNFILLED).all()
+        assert int((gc.wave_sized(dg, 4096) & ~far).sum()) >= 10 and int(((dg["a"] == 0) != (dg["b"] == 0)).sum()) >= 20
+        assert int((gc.wave_sized(sg, 512) & (gc.trace_words(sg) > gc.TRACE_LDS_WORDS)).sum()) == 2
+        (s_ops, s_all), (d_ops, d_all) = op_lengths(step), op_lengths(d)
+        assert s_ops[OP_EQ] >= 0.95 * s_all and s_ops[OP_EQ] < s_all and d_ops[OP_I] + d_ops[OP_D] >= 0.5 * d_all, (step.name, s_ops, d_ops)
+
+    def last_read_does_not_fit(step, d):
+        seen = step.family.seen[step.nreads]
+        lost = (step.want["records"]["ref_start"] == np.uint64(UNALIGNED)) & (seen["reference"]["ref_start"] != np.uint64(UNALIGNED))
+        assert seen["op_cap"] == int(seen["ooffs"][-1]) - 1 and lost.sum() == 1 and 0 < step.want["entries"].size <= seen["op_cap"]
+        assert int(d.want["op_offsets"][-1]) > 4 * int(seen["ooffs"][-1]) and d.nreads < step.nreads  # other offsets, fewer reads
+
+    add(Cigar(cat, "dirty: cigar_device at max_fill 4 096, traces in device memory, lopsided gaps", "real", g_dirty, AlignParams(4096)), None,
+        as_dirtier=True)
+    add(Cigar(cat, "cigar_device, max_fill 512, nearly all '='", "real", g_step),
+        "dirty: cigar_device at max_fill 4 096, traces in device memory, lopsided gaps", other_stride)
+    add(Cigar(cat, "cigar_device, op_capacity short of the last read", "real", g_step, short_ops=True),
+        "dirty: cigar_device at max_fill 4 096, traces in device memory, lopsided gaps", last_read_does_not_fit)
+    both(Cigar(cat, "cigar_host", "real", None, form="host", batch=mbatch, min_length=8),
+         Cigar(cat, "dirty: cigar_host on reads with ten times the edits", "real", None, form="host", batch=mmany, min_length=6),
+         ten_times_the_edits)
+
     for s in list(cat.steps.values()) + list(cat.dirtiers.values()):
         assert s.dirtier is None or s.dirtier in cat.dirtiers, (s.name, s.dirtier)
     return cat
