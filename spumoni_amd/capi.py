@@ -792,6 +792,83 @@ class Index:
         out["step_ms"] = list(s.step_ms)
         return out
 
+    # -- extended CIGARs (include/spumoni_extend.h) ----------------------------------
+    def extend_device(self, d_reads, d_read_offsets, d_matches, d_match_offsets, d_chains, d_pred, params=None, extend_params=None,
+                      gap_capacity=None, op_capacity=None, d_out=None, d_out_op_offsets=None, d_out_ops=None, d_out_ends=None,
+                      want_ends=True, stream=None):
+        """cigar_device's results with both ends of every alignment extended and the rest of the read soft-clipped
+        (extend.py), from the same inputs.  Returns (d_out int32 (reads, 12), d_out_op_offsets int64[reads + 1], d_out_ops
+        int32[op_capacity], d_out_ends int32 (2 * reads, 4) or None without want_ends); gap_capacity defaults to the
+        number of matches, op_capacity to cigar_device's default plus two clips a read.  params: (max_fill,),
+        extend_params: (max_extend, band, mismatch, indel), or None for the defaults."""
+        import torch
+
+        from .align import AlignParams
+        from .extend import ExtendParams
+
+        L = _spe()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = d_match_offsets.device
+        nreads = d_match_offsets.numel() - 1
+        if gap_capacity is None:
+            gap_capacity = d_matches.numel() // 4
+        if op_capacity is None:
+            op_capacity = 2 * d_reads.numel() + 2 * (d_matches.numel() // 4) + 3 * max(nreads, 0)
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 12), dtype=torch.int32, device=dev)
+        if d_out_op_offsets is None:
+            d_out_op_offsets = torch.empty(max(nreads, 0) + 1, dtype=torch.int64, device=dev)
+        if d_out_ops is None:
+            d_out_ops = torch.empty(max(int(op_capacity), 1), dtype=torch.int32, device=dev)
+        if d_out_ends is None and want_ends:
+            d_out_ends = torch.empty((2 * max(nreads, 0), 4), dtype=torch.int32, device=dev)
+        p = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        ep = SpeParams(*(int(v) for v in (ExtendParams() if extend_params is None else extend_params)))
+        _check(L.spe_extend_device(self._h, _t_ptr(d_reads), _t_ptr(d_read_offsets), _t_ptr(d_matches), _t_ptr(d_match_offsets), nreads,
+                                   _t_ptr(d_chains), _t_ptr(d_pred), C.byref(p), C.byref(ep), int(gap_capacity), int(op_capacity),
+                                   _t_ptr(d_out), _t_ptr(d_out_op_offsets), _t_ptr(d_out_ops), _t_ptr(d_out_ends),
+                                   C.c_void_p(st.cuda_stream)))
+        return d_out, d_out_op_offsets, d_out_ops, d_out_ends
+
+    def extend_host(self, seqs, offs, min_length, chain_params=None, params=None, extend_params=None, digest=None, want_docs=False):
+        """spe_extend_begin + spe_extend_fetch: reads in, cigar_host's tuple plus the ends out: (records
+        align.ALIGN_DTYPE[reads], op_offsets uint64[reads + 1], entries uint32[op_offsets[-1]], chains
+        chain.CHAIN_DTYPE[reads], values uint64[reads], ends extend.END_DTYPE[2 * reads]).  digest: (kind, k, w) or None."""
+        from .align import ALIGN_DTYPE, AlignParams
+        from .chain import CHAIN_DTYPE, ChainParams
+        from .extend import END_DTYPE, ExtendParams
+
+        L = _spe()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        rec = np.zeros(max(nreads, 1), dtype=ALIGN_DTYPE)
+        chains = np.zeros(max(nreads, 1), dtype=CHAIN_DTYPE)
+        vals = np.zeros(max(nreads, 1), dtype=np.uint64)
+        ends = np.zeros(2 * max(nreads, 1), dtype=END_DTYPE)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        ep = SpeParams(*(int(v) for v in (ExtendParams() if extend_params is None else extend_params)))
+        n = C.c_uint64(0)
+        _check(L.spe_extend_begin(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                  C.byref(cp), C.byref(ap), C.byref(ep), _np_ptr(rec), _np_ptr(chains), _np_ptr(vals), _np_ptr(ends),
+                                  C.byref(n)))
+        op_offsets = np.zeros(max(nreads, 0) + 1, dtype=np.uint64)
+        ops = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(L.spe_extend_fetch(self._h, _np_ptr(op_offsets), _np_ptr(ops)))
+        return rec[:nreads], op_offsets, ops[:n.value], chains[:nreads], vals[:nreads], ends[:2 * nreads]
+
+    def extend_stats(self) -> dict:
+        """Of the most recent extend_device / extend_host call: cigar_stats' counts, the ends looked at and extended, the
+        band cells, the clipped characters, the error and overflow flags, kernel time and the time of the six steps (cigar's
+        five, then the ends)."""
+        s = SpeExtendStats()
+        _check(_spe().spe_last_extend_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpeExtendStats._fields_ if f[0] != "reserved"}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -1010,6 +1087,44 @@ def _spg() -> C.CDLL:
         L.spg_cigar_fetch.argtypes = [vp, vp, vp]
         L.spg_last_cigar_stats.argtypes = [vp, C.POINTER(SpgCigarStats)]
         _SPG_READY = True
+    return L
+
+
+# ---- the extended CIGARs (include/spumoni_extend.h) -----------------------------------------------------------------
+EXTEND_EXPORTS = ["spe_extend_device", "spe_extend_begin", "spe_extend_fetch", "spe_last_extend_stats"]
+_SPE_READY = False
+
+
+class SpeParams(C.Structure):
+    _fields_ = [("max_extend", C.c_uint32), ("band", C.c_uint32), ("mismatch", C.c_uint32), ("indel", C.c_uint32)]
+
+
+class SpeEnd(C.Structure):
+    _fields_ = [("read_chars", C.c_uint32), ("text_chars", C.c_uint32), ("score", C.c_int32), ("edits", C.c_uint32)]
+
+
+class SpeExtendStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("aligned_reads", C.c_uint64), ("gaps", C.c_uint64), ("filled_gaps", C.c_uint64),
+                ("cells", C.c_uint64), ("entries", C.c_uint64), ("path_words", C.c_uint64), ("ends", C.c_uint64),
+                ("extended_ends", C.c_uint64), ("band_cells", C.c_uint64), ("clipped", C.c_uint64), ("error", C.c_uint32),
+                ("overflow", C.c_uint32), ("kernel_ms", C.c_float), ("step_ms", C.c_float * 6), ("reserved", C.c_uint32)]
+
+
+def _spe() -> C.CDLL:
+    """The library with the spe_* argtypes set (on first use)."""
+    global _SPE_READY
+    L = lib()
+    if not hasattr(L, "spe_extend_begin"):
+        raise SpxError(f"{LIB_PATH} has no extend kernels (spe_extend_begin): there is no CPU fallback")
+    if not _SPE_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spe_extend_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, C.POINTER(SpaParams), C.POINTER(SpeParams), u64, u64, vp, vp,
+                                        vp, vp, vp]
+        L.spe_extend_begin.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams),
+                                       C.POINTER(SpeParams), vp, vp, vp, vp, C.POINTER(u64)]
+        L.spe_extend_fetch.argtypes = [vp, vp, vp]
+        L.spe_last_extend_stats.argtypes = [vp, C.POINTER(SpeExtendStats)]
+        _SPE_READY = True
     return L
 
 

@@ -1,0 +1,181 @@
+// extend_main.cpp -- `spumoni extend`: one line per read -- `spumoni cigar`'s columns with the alignment taken to the
+// read's ends: both ends of the chain extended by a banded dynamic programme, the spans, matches and edits with the
+// extensions in them, and what is left of the read on either side as soft clips (S), so that the CIGAR accounts for every
+// read character (include/spumoni_extend.h has the rule).  The reads come from reads.cpp (same ids, same FASTA / FASTQ
+// quirks as `run`), the MS index through the loaders `run` uses, and super-batches of SPUMONI_SUPER_BATCH characters go
+// through spe_extend_begin / spe_extend_fetch in calls of one piece each.  The driver is read_command.cpp; a run that
+// fails leaves no file.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../../include/spumoni_extend.h"
+#include "read_command.hpp"
+
+using namespace spumoni_host;
+
+namespace {
+
+int spumoni_extend_usage() {
+    std::fprintf(stderr, "spumoni extend - Uses a spumoni MS index to align each read along the best chain of its matches with the reference, extends the alignment to the read's ends and reports it as a CIGAR with soft clips.\n");
+    std::fprintf(stderr, "Usage: spumoni extend [options]\n\n");
+    std::fprintf(stderr, "Options:\n");
+    std::fprintf(stderr, "\t%-35sprints this usage message\n", "-h, --help");
+    std::fprintf(stderr, "\t%-25s%-10soutput prefix used for index\n", "-r, --ref", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10spath to patterns file that will be used.\n", "-p, --pattern", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10sturn off minimizer digestion of reads (default: on)\n", "-n, --no-digest", "");
+    std::fprintf(stderr, "\t%-25s%-10suse alphabet-promoted minimizers\n", "-m, --minimizer-alphabet", "");
+    std::fprintf(stderr, "\t%-25s%-10suse DNA-letter based minimizers\n", "-a, --dna-minimizer", "");
+    std::fprintf(stderr, "\t%-25s%-10ssmall window size (k) for finding minimizers (default: 4)\n", "-K, --small-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10slarge window size (w) for finding minimizers (default: 11)\n", "-W, --large-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10suse document array: matches chain within one document, and the alignment names it\n", "-d, --doc-array", "");
+    std::fprintf(stderr, "\t%-25s%-10sa match is an anchor when it is at least this long, 1 or more (default: the\n", "-L, --min-length", "[INT]");
+    std::fprintf(stderr, "\t%-35sMS threshold `run -c` classifies with, from the null database)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest distance between two chained anchors in the read and in the text,\n", "-S, --max-dist", "[INT]");
+    std::fprintf(stderr, "\t%-35s1 .. 2147483647 (default: 5000)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest difference of those two distances, 0 .. 2147483647 (default: 500)\n", "-G, --max-gap", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat a unit of that difference costs, 0 .. 65535 (default: 1)\n", "-B, --gap-penalty", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10spredecessors an anchor looks back at, 1 .. 64 (default: 64)\n", "-H, --lookback", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10sa gap between two anchors is filled when neither side is longer, 1 .. 4096\n", "-F, --max-fill", "[INT]");
+    std::fprintf(stderr, "\t%-35s(default: 512)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest end side that is extended, 1 .. 4096 (default: 512)\n", "-E, --max-extend", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10show far an extension may drift off the diagonal, 0 .. 63 (default: 16)\n", "-O, --band", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat an unequal column of an extension costs, 0 .. 65535 (default: 4)\n", "-N, --mismatch", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat an inserted or deleted character of an extension costs, 0 .. 65535\n", "-I, --indel", "[INT]");
+    std::fprintf(stderr, "\t%-35s(default: 6); an equal column scores 1\n\n", "");
+    std::fprintf(stderr, "Matching statistics (-M) are implied. Writes <pattern>.extended: id, values, read_start, read_end, ref_start,\n");
+    std::fprintf(stderr, "ref_end, matches, edits, anchors, unfilled, skipped[, doc], length and the CIGAR per read, positions in the\n");
+    std::fprintf(stderr, "(digested) read and text; length is the read's length in values, so that a line can be checked on its own: the\n");
+    std::fprintf(stderr, "CIGAR's = X I and S add up to it. The operations are = X I D, N for the text side of a gap that is not filled, and\n");
+    std::fprintf(stderr, "S for the read characters outside the alignment; a run is at most 268435455 long and a longer one is printed as\n");
+    std::fprintf(stderr, "several. A read without a match has -1 for ref_start (and doc), zeros elsewhere and * for the CIGAR.\n\n");
+    return 1;
+}
+
+}  // namespace
+
+int extend_main(int argc, char** argv) {
+    if (argc == 1) return spumoni_extend_usage();
+    ReadOptions o;
+    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
+    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6;
+    parse_read_options(argc, argv, o, spumoni_extend_usage, true, "L:S:G:B:H:F:E:O:N:I:",
+                       {{"min-length", required_argument, NULL, 'L'},
+                        {"max-dist", required_argument, NULL, 'S'},
+                        {"max-gap", required_argument, NULL, 'G'},
+                        {"gap-penalty", required_argument, NULL, 'B'},
+                        {"lookback", required_argument, NULL, 'H'},
+                        {"max-fill", required_argument, NULL, 'F'},
+                        {"max-extend", required_argument, NULL, 'E'},
+                        {"band", required_argument, NULL, 'O'},
+                        {"mismatch", required_argument, NULL, 'N'},
+                        {"indel", required_argument, NULL, 'I'}},
+                       [&](int c, const char* arg) {
+                           if (c == 'L') {
+                               o.have_threshold = true;
+                               o.threshold = std::strtoull(arg, nullptr, 10);
+                           } else {
+                               (c == 'S'   ? max_dist
+                                : c == 'G' ? max_gap
+                                : c == 'B' ? gap_penalty
+                                : c == 'H' ? lookback
+                                : c == 'F' ? max_fill
+                                : c == 'E' ? max_extend
+                                : c == 'O' ? band
+                                : c == 'N' ? mismatch
+                                           : indel) = arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
+                           }
+                       });
+    require_ref_and_pattern(o);
+    if (o.pml_requested)
+        fatal_warning("-P cannot be used with `spumoni extend`: the anchors are read off matching statistics (-M is implied); "
+                      "PMLs have no pointers.");
+    o.ms = true;
+    validate_read_options(o);
+    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
+    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
+    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
+    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
+    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
+    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
+    if (max_extend < 1 || max_extend > 4096) fatal_warning("the largest extended end (-E) must be between 1 and 4096.");
+    if (band > 63) fatal_warning("the band (-O) must be between 0 and 63.");
+    if (mismatch > 65535) fatal_warning("the mismatch cost (-N) must be between 0 and 65535.");
+    if (indel > 65535) fatal_warning("the indel cost (-I) must be between 0 and 65535.");
+    o.ref_file += o.use_promotions ? ".bin" : ".fa";
+    const std::vector<void*> entry = device_entry_points("extend", {"spe_extend_begin", "spe_extend_fetch"}, "the extend kernels");
+    auto extend_begin = reinterpret_cast<decltype(&spe_extend_begin)>(entry[0]);
+    auto extend_fetch = reinterpret_cast<decltype(&spe_extend_fetch)>(entry[1]);
+    ReadRun run;
+    open_read_run(o, 8u << 20, run);
+    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spe_extend_begin)
+    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
+    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
+    const spa_params fill{(uint32_t)max_fill};
+    const spe_params ends{(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel};
+    std::fprintf(stderr, "[extend] index loaded (n = %llu, r = %llu); a match is an anchor from length %llu on (max-dist %llu, max-gap %llu, "
+                 "gap penalty %llu, lookback %llu, max-fill %llu, max-extend %llu, band %llu, mismatch %llu, indel %llu)\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)min_length, max_dist, max_gap,
+                 gap_penalty, lookback, max_fill, max_extend, band, mismatch, indel);
+
+    LinesFile out;
+    out.open(o.pattern_file + ".extended", false);
+    uint64_t num_reads = 0, num_aligned = 0, num_entries = 0, num_clipped = 0;
+    std::vector<spa_alignment> recs;
+    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
+    std::vector<uint32_t> ops;
+    static const char op_char[16] = {'?', 'I', 'D', 'N', 'S', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    scan_reads(
+        run, out,
+        [&](ReadBatch& b) {
+            recs.resize(b.take + 1);
+            op_offs.assign(b.take + 1, 0);
+            ops.clear();
+            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
+            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
+                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+                uint64_t n = 0;
+                if (extend_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
+                                 min_length, o.use_doc ? 1 : 0, &params, &fill, &ends, recs.data() + q0, nullptr,
+                                 b.values.data() + q0, nullptr, &n) != SPX_OK)
+                    fatal_error("%s", spx_last_error());
+                const size_t at = ops.size();
+                ops.resize(at + n + 1);
+                piece_offs.resize(q1 - q0 + 1);
+                if (extend_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
+                ops.resize(at + n);
+                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
+            }
+        },
+        [&](const ReadBatch& b, size_t i) {
+            const spa_alignment& c = recs[i];
+            const bool aligned = c.ref_start != SPA_UNALIGNED;
+            std::fwrite(b.recs[i].id, 1, b.recs[i].id_len, out.f);
+            std::fprintf(out.f, "\t%llu\t%u\t%u\t", (unsigned long long)b.values[i], c.read_start, c.read_end);
+            if (aligned)
+                std::fprintf(out.f, "%llu", (unsigned long long)c.ref_start);
+            else
+                std::fputs("-1", out.f);
+            std::fprintf(out.f, "\t%llu\t%u\t%u\t%u\t%u\t%u", (unsigned long long)c.ref_end, c.matches, c.edits, c.anchors, c.unfilled,
+                         c.skipped);
+            if (o.use_doc) std::fprintf(out.f, "\t%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
+            std::fprintf(out.f, "\t%llu\t", (unsigned long long)b.values[i]);
+            if (op_offs[i] == op_offs[i + 1]) std::fputc('*', out.f);
+            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e) {
+                std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
+                if ((ops[e] & 15) == SPE_OP_S) num_clipped += ops[e] >> 4;
+            }
+            std::fputc('\n', out.f);
+            num_entries += op_offs[i + 1] - op_offs[i];
+            num_aligned += aligned;
+            num_reads++;
+        });
+    std::fprintf(stderr, "[extend] %llu reads, %llu aligned, %llu without a match, %llu CIGAR entries, %llu characters clipped (%.3f sec). "
+                 "results are saved in *.extended\n",
+                 (unsigned long long)num_reads, (unsigned long long)num_aligned, (unsigned long long)(num_reads - num_aligned),
+                 (unsigned long long)num_entries, (unsigned long long)num_clipped,
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count());
+    return 0;
+}

@@ -320,7 +320,7 @@ struct spx_index {
     // beyond Product::acc (path words, the bound of the entries, the ticks of fill and walk back); and the entries that
     // wait for spg_cigar_fetch
     enum { TB_CNT, TB_GOFFS, TB_GAPS, TB_DESC, TB_LIST, TB_CUB, TB_PW, TB_POFFS, TB_PATH, TB_TRACE, TB_OCNT, TB_CHAINS, TB_OUT,
-           TB_PRED, TB_OOFFS, TB_OPS, TB_COUNT };
+           TB_PRED, TB_OOFFS, TB_OPS, TB_EPW, TB_EPOFFS, TB_ERES, TB_ETRACE, TB_ENDS, TB_COUNT };
     Scratch cigar_scr[TB_COUNT];
     Product cigar;  // acc: reads, aligned reads, gaps, filled gaps, cells, entries
     hipEvent_t ev_cigar[7] = {};
@@ -329,6 +329,18 @@ struct spx_index {
     uint64_t cigar_extra[4] = {};
     bool cigar_ready = false;
     uint64_t cigar_ready_n = 0, cigar_ready_reads = 0;
+    // extended CIGARs (spx_extend.hip): the same set once more, the product's own (both drive the code of
+    // spx_cigar_kernels.h through a TraceView), with the slots only this product fills: each end's words of path and their
+    // offsets, the ends' results, the trace buffers of the ends' wavefronts (under mu) and spe_extend_begin's ends (under
+    // host_mu); an eighth event in front of the ends' step, its time, and the ends' four counters
+    Scratch extend_scr[TB_COUNT];
+    Product extend;  // acc: as cigar's
+    hipEvent_t ev_extend[8] = {};
+    bool extend_phase[2] = {false, false};
+    float extend_step_ms[6] = {};
+    uint64_t extend_extra[8] = {};
+    bool extend_ready = false;
+    uint64_t extend_ready_n = 0, extend_ready_reads = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -464,6 +476,8 @@ int chain_check_params(const spx_index* ix, const struct ::spc_params* p);
 void release_align(spx_index* ix);
 // spx_cigar.hip: the same for the CIGARs
 void release_cigar(spx_index* ix);
+// spx_extend.hip: the same for the extended CIGARs
+void release_extend(spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on
