@@ -49,6 +49,11 @@ int spr_text_stats(const spr_text *t, uint64_t *n_text, uint64_t *n_seqs, uint64
  * cumulative ends of the sequences in fwd; seq_file: n_seqs file numbers. */
 int spr_text_copy(const spr_text *t, uint8_t *text, uint64_t *file_text_lengths, uint8_t *fwd, uint64_t *seq_ends,
                   uint32_t *seq_file);
+/* The sequences' names, for the sequence table of `spumoni build -s` (spumoni_amd/map.py: sequence_name): a header's
+ * bytes behind '>' up to the first ASCII whitespace; seq<k>, k the sequence's 1-based ordinal over all files, for an
+ * empty name and for the lines before a file's first header.  Each pointer may be NULL.  n_name_bytes: the bytes of all
+ * names together; names: those bytes, name after name; name_ends: n_seqs cumulative ends of the names in `names`. */
+int spr_text_names(const spr_text *t, uint8_t *names, uint64_t *name_ends, uint64_t *n_name_bytes);
 void spr_text_free(spr_text *t);
 
 #ifdef __cplusplus

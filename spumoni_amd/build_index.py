@@ -18,6 +18,9 @@ It writes exactly the files `spumoni run` (ours) consumes, under `<prefix>.fa*`:
   spumoni_null_reads.fa    (next to the prefix) the null reads the statistics were taken from, chosen the way
                            src/refbuilder.cpp:83-127 / :234-270 chooses them (srand(0), rand() of glibc)
   .fa.doc / .fa.fdi        document array (src/doc_array.cpp) when --doc
+  .fa.seqs                 the sequence table `spumoni map` needs, when --seq-table: name<TAB>length<TAB>text_start<TAB>strands
+                           per non-empty sequence, in text order (spumoni_amd/map.py; refused under -m / -a: digested
+                           coordinates cannot be turned back into bases)
 
 The text is each sequence followed by its reverse complement, no separators, upper-cased (the order
 src/refbuilder.cpp:100-180 writes them in); the BWT / thresholds / samples are computed here by suffix sorting, not by
@@ -63,6 +66,23 @@ def read_fasta(path, upper=True):
     if cur:
         seqs.append(b"".join(cur))
     return [np.frombuffer(s.upper() if upper else s, dtype=np.uint8) for s in seqs if len(s)]
+
+
+def read_fasta_names(path):
+    """The names of the sequences read_fasta returns, by its own line rules: one header (the bytes behind '>', None for the
+    lines before the first header) per sequence that has a character."""
+    headers, cur, has = [], None, False
+    with _open_maybe_gz(path) as f:
+        for line in f:
+            if line.startswith(b">"):
+                if has:
+                    headers.append(cur)
+                cur, has = line[1:].rstrip(b"\n"), False
+            elif line.strip():
+                has = True
+    if has:
+        headers.append(cur)
+    return headers
 
 
 class GlibcRand:
@@ -268,6 +288,8 @@ def main(argv=None):
     ap.add_argument("-o", "--output", required=True, help="output prefix")
     ap.add_argument("--no-rev-comp", action="store_true")
     ap.add_argument("--doc", action="store_true", help="also write the document array")
+    ap.add_argument("--seq-table", action="store_true",
+                    help="also write <prefix>.fa.seqs, the sequence table `spumoni map` needs (not with -m / -a)")
     ap.add_argument("--null-reads", type=int, default=None, help="keep only the first N null reads (default: all, at most ~1000)")
     ap.add_argument("-w", "--window", type=int, default=150, help="bin size of the KS fit (50-400)")
     ap.add_argument("-m", "--minimizer-alphabet", action="store_true",
@@ -282,6 +304,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.minimizer_alphabet and a.dna_minimizer:
         ap.error("only one of -m / -a")
+    if a.seq_table and (a.minimizer_alphabet or a.dna_minimizer):
+        ap.error("--seq-table cannot be used with a digestion (-m / -a): digested coordinates cannot be turned back into bases")
     digest_kind = capi.SPX_DIGEST_PROMOTED if a.minimizer_alphabet else capi.SPX_DIGEST_DNA if a.dna_minimizer else 0
     digester = capi.digester(0) if digest_kind else None
     files, doc_ids = [a.ref] if a.ref else [], []
@@ -307,10 +331,19 @@ def main(argv=None):
     if not files:
         ap.error("give -r or -l")
     parts, doc_lengths, files_seqs = [], [], []
+    seq_names, seq_lengths = [], []
     for fi, fpath in enumerate(files):
         total = 0
         seqs = read_fasta(fpath)
         files_seqs.append(seqs)
+        if a.seq_table:
+            from .map import sequence_name
+
+            headers = read_fasta_names(fpath)
+            assert len(headers) == len(seqs)
+            for h, s in zip(headers, seqs):
+                seq_lengths.append(s.size)
+                seq_names.append(sequence_name(h, len(seq_lengths)))
         for s in seqs:
             pieces = [s] if a.no_rev_comp else [s, synth.revcomp(s)]
             for p in pieces:
@@ -350,6 +383,10 @@ def main(argv=None):
         heads = np.maximum(raw.heads.numpy(), 1)
         write_thrbv(prefix + ".thrbv.spumoni", heads, raw.lens.numpy(), raw.thr.numpy())
         write_thrbv(prefix + ".thrbv.ms", heads, raw.lens.numpy(), raw.thr.numpy(), raw.ssa.numpy(), raw.esa.numpy())
+    if a.seq_table:
+        from .map import write_seq_table
+
+        write_seq_table(prefix + ".seqs", seq_names, seq_lengths, 1 if a.no_rev_comp else 2)
     if a.doc:
         write_doc_array(prefix + ".doc", raw.doc_start.tolist(), raw.doc_end.tolist(), len(doc_lengths))
     # empirical null (compute_ms_pml.cpp:1409-1506): the null reads upper-cased, reversed, digested like the text;

@@ -869,6 +869,74 @@ class Index:
         out["step_ms"] = list(s.step_ms)
         return out
 
+    # -- mappings (include/spumoni_map.h) ----------------------------------------------
+    def set_sequences(self, seq_lengths, strands: int) -> None:
+        """The sequence table (map.read_seq_table's lengths and strands): copied to the device and held in the handle."""
+        lengths = np.ascontiguousarray(seq_lengths, dtype=np.uint64)
+        _check(_spn().spn_set_sequences(self._h, _np_ptr(lengths), lengths.size, int(strands)))
+
+    def map_device(self, d_alignments, d_op_offsets, d_ops, d_read_offsets, op_capacity=None, in_entries=None, d_out=None,
+                   d_out_op_offsets=None, d_out_ops=None, stream=None):
+        """extend_device's (d_out, d_out_op_offsets, d_out_ops) and the reads' offsets in, the mappings out (map.py):
+        (d_out int32 (reads, 12), a view of map.MAPPING_DTYPE; d_out_op_offsets int64[reads + 1]; d_out_ops
+        int32[op_capacity]).  in_entries defaults to d_ops' size, op_capacity to in_entries plus two a read."""
+        import torch
+
+        L = _spn()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = d_read_offsets.device
+        nreads = d_read_offsets.numel() - 1
+        if in_entries is None:
+            in_entries = d_ops.numel()
+        if op_capacity is None:
+            op_capacity = int(in_entries) + 2 * max(nreads, 0)
+        if d_out is None:
+            d_out = torch.empty((max(nreads, 0), 12), dtype=torch.int32, device=dev)
+        if d_out_op_offsets is None:
+            d_out_op_offsets = torch.empty(max(nreads, 0) + 1, dtype=torch.int64, device=dev)
+        if d_out_ops is None:
+            d_out_ops = torch.empty(max(int(op_capacity), 1), dtype=torch.int32, device=dev)
+        _check(L.spn_map_device(self._h, _t_ptr(d_alignments), _t_ptr(d_op_offsets), _t_ptr(d_ops), int(in_entries),
+                                _t_ptr(d_read_offsets), nreads, int(op_capacity), _t_ptr(d_out), _t_ptr(d_out_op_offsets),
+                                _t_ptr(d_out_ops), C.c_void_p(st.cuda_stream)))
+        return d_out, d_out_op_offsets, d_out_ops
+
+    def map_host(self, seqs, offs, min_length, chain_params=None, params=None, extend_params=None, digest=None, want_docs=False):
+        """spn_map_begin + spn_map_fetch: reads in, (mappings map.MAPPING_DTYPE[reads], op_offsets uint64[reads + 1],
+        entries uint32[op_offsets[-1]], alignments align.ALIGN_DTYPE[reads]) out.  digest: (kind, k, w) or None."""
+        from .align import ALIGN_DTYPE, AlignParams
+        from .chain import ChainParams
+        from .extend import ExtendParams
+        from .map import MAPPING_DTYPE
+
+        L = _spn()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        out = np.zeros(max(nreads, 1), dtype=MAPPING_DTYPE)
+        rec = np.zeros(max(nreads, 1), dtype=ALIGN_DTYPE)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        ep = SpeParams(*(int(v) for v in (ExtendParams() if extend_params is None else extend_params)))
+        n = C.c_uint64(0)
+        _check(L.spn_map_begin(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                               C.byref(cp), C.byref(ap), C.byref(ep), _np_ptr(out), _np_ptr(rec), C.byref(n)))
+        op_offsets = np.zeros(max(nreads, 0) + 1, dtype=np.uint64)
+        ops = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(L.spn_map_fetch(self._h, _np_ptr(op_offsets), _np_ptr(ops)))
+        return out[:nreads], op_offsets, ops[:n.value], rec[:nreads]
+
+    def map_stats(self) -> dict:
+        """Of the most recent map_device / map_host call: the reads, the mapped, cut and reverse-strand reads, the entries
+        in and out, the characters that cuts clipped, the error and overflow flags, kernel time and the time of the two
+        steps (locate and count, write)."""
+        s = SpnMapStats()
+        _check(_spn().spn_last_map_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpnMapStats._fields_ if f[0] != "reserved"}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -1128,6 +1196,35 @@ def _spe() -> C.CDLL:
     return L
 
 
+# ---- the mappings (include/spumoni_map.h) -------------------------------------------------------------------------
+MAP_EXPORTS = ["spn_set_sequences", "spn_map_device", "spn_map_begin", "spn_map_fetch", "spn_last_map_stats"]
+_SPN_READY = False
+
+
+class SpnMapStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("mapped", C.c_uint64), ("cut_reads", C.c_uint64), ("reverse_reads", C.c_uint64),
+                ("entries_in", C.c_uint64), ("entries_out", C.c_uint64), ("cut_chars", C.c_uint64), ("error", C.c_uint32),
+                ("overflow", C.c_uint32), ("kernel_ms", C.c_float), ("step_ms", C.c_float * 2), ("reserved", C.c_uint32)]
+
+
+def _spn() -> C.CDLL:
+    """The library with the spn_* argtypes set (on first use)."""
+    global _SPN_READY
+    L = lib()
+    if not hasattr(L, "spn_map_begin"):
+        raise SpxError(f"{LIB_PATH} has no map kernels (spn_map_begin): there is no CPU fallback")
+    if not _SPN_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spn_set_sequences.argtypes = [vp, vp, u64, u32]
+        L.spn_map_device.argtypes = [vp, vp, vp, vp, u64, vp, u64, u64, vp, vp, vp, vp]
+        L.spn_map_begin.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams),
+                                    C.POINTER(SpeParams), vp, vp, C.POINTER(u64)]
+        L.spn_map_fetch.argtypes = [vp, vp, vp]
+        L.spn_last_map_stats.argtypes = [vp, C.POINTER(SpnMapStats)]
+        _SPN_READY = True
+    return L
+
+
 # ---- the index builder (include/spumoni_build.h) -------------------------------------------------------------------
 _SPB_READY = False
 
@@ -1192,7 +1289,7 @@ def build_raw(text, doc_lengths=None, with_samples: bool = True, device: int = 0
 
 
 # ---- reference text preparation (include/spumoni_reftext.h) -------------------------------------------------------
-REFTEXT_EXPORTS = ["spr_text_from_fasta", "spr_text_stats", "spr_text_copy", "spr_text_free"]
+REFTEXT_EXPORTS = ["spr_text_from_fasta", "spr_text_stats", "spr_text_copy", "spr_text_names", "spr_text_free"]
 _SPR_READY = False
 
 
@@ -1208,6 +1305,7 @@ def _spr() -> C.CDLL:
         L.spr_text_from_fasta.argtypes = [vp, u64, vp, u32, C.c_int, C.c_int, u32, u32, u64, C.c_int]
         L.spr_text_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.spr_text_copy.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.spr_text_names.argtypes = [vp, vp, vp, C.POINTER(u64)]
         L.spr_text_free.argtypes = [vp]
         _SPR_READY = True
     return L
@@ -1217,7 +1315,7 @@ def prepare_fasta(files, rev_comp: bool = True, digest_kind: int = 0, k: int = 4
                   device: int = 0):
     """The text `spumoni build` indexes from FASTA file contents (a list of bytes, already inflated), prepared on the
     device: a dict with "text", "file_text_lengths", "fwd" (the sequences, case preserved, back to back), "seq_ends"
-    and "seq_file" (numpy arrays)."""
+    and "seq_file" (numpy arrays), and "names" (a list of bytes: map.sequence_name of every sequence)."""
     data = np.frombuffer(b"".join(files), dtype=np.uint8)
     ends = np.ascontiguousarray(np.cumsum([len(f) for f in files]), dtype=np.uint64)
     L = _spr()
@@ -1233,6 +1331,12 @@ def prepare_fasta(files, rev_comp: bool = True, digest_kind: int = 0, k: int = 4
                "seq_file": np.empty(ns.value, dtype=np.uint32)}
         _check(L.spr_text_copy(h, *[_np_ptr(out[x]) for x in ("text", "file_text_lengths", "fwd", "seq_ends",
                                                                 "seq_file")]))
+        nb = C.c_uint64()
+        _check(L.spr_text_names(h, None, None, C.byref(nb)))
+        names, name_ends = np.empty(nb.value, dtype=np.uint8), np.empty(ns.value, dtype=np.uint64)
+        _check(L.spr_text_names(h, _np_ptr(names), _np_ptr(name_ends), None))
+        cuts = [0] + name_ends.tolist()
+        out["names"] = [names[a:b].tobytes() for a, b in zip(cuts, cuts[1:])]
     finally:
         L.spr_text_free(h)
     return out

@@ -23,6 +23,7 @@
 #include <fstream>
 #include <map>
 #include <sstream>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -97,6 +98,8 @@ int spumoni_build_usage() {
     std::fprintf(stderr, "\t%-25s%-10sbuild an index that can be used to compute PMLs\n", "-P, --PML", "");
     std::fprintf(stderr, "\t%-25s%-10skeep the temporary files (default: false)\n", "-k, --keep", "");
     std::fprintf(stderr, "\t%-25s%-10sbuild the document array (default: false)\n", "-d, --doc-array", "");
+    std::fprintf(stderr, "\t%-25s%-10swrite the sequence table <prefix>.fa.seqs that `spumoni map` needs: name, length,\n"
+                         "\t%-35stext start and strands per sequence; only with -n (default: false)\n", "-s, --seq-table", "", "");
     std::fprintf(stderr, "\t%-25s%-10ssize of windows in bp for classification (default: 150)\n\n", "-w, --window",
                  "[INT]");
     std::fprintf(stderr, "\tPFP-related options:\n");
@@ -109,7 +112,7 @@ struct BuildOptions {  // SpumoniBuildOptions (include/spumoni_main.hpp:130-225)
     size_t hash_mod = 100;
     bool keep_files = false, ms_index = false, pml_index = false, verbose = false, is_fasta = false;
     bool build_doc = false, use_minimizers = true, use_promotions = false, use_dna_letters = false;
-    bool is_general_text = false, use_rev_comp = true;
+    bool is_general_text = false, use_rev_comp = true, seq_table = false;
     size_t k = 4, w = 11, bin_size = 150;
 
     void validate() {
@@ -169,11 +172,12 @@ void parse_build_options(int argc, char** argv, BuildOptions* opts) {
                                            {"PML", no_argument, NULL, 'P'},
                                            {"keep", no_argument, NULL, 'k'},
                                            {"doc-array", no_argument, NULL, 'd'},
+                                           {"seq-table", no_argument, NULL, 's'},
                                            {"window", required_argument, NULL, 'w'},
                                            {"hash-mod", required_argument, NULL, 'p'},
                                            {0, 0, 0, 0}};
     int long_index = 0;
-    for (int c; (c = getopt_long(argc, argv, "ho:r:MPw:kdi:b:nvmK:W:tgcp:", long_options, &long_index)) >= 0;) {
+    for (int c; (c = getopt_long(argc, argv, "ho:r:MPw:kdi:b:nvmK:W:tgcp:s", long_options, &long_index)) >= 0;) {
         switch (c) {
             case 'h': spumoni_build_usage(); std::exit(1);
             case 'o': opts->output_prefix.assign(optarg); break;
@@ -194,6 +198,7 @@ void parse_build_options(int argc, char** argv, BuildOptions* opts) {
             case 'p': opts->hash_mod = std::max(std::atoi(optarg), 1); break;
             case 'k': opts->keep_files = true; break;
             case 'd': opts->build_doc = true; break;
+            case 's': opts->seq_table = true; break;
             default: spumoni_build_usage(); std::exit(1);
         }
     }
@@ -205,6 +210,7 @@ struct DeviceBuilder {
     decltype(&spr_text_stats) text_stats;
     decltype(&spr_text_copy) text_copy;
     decltype(&spr_text_free) text_free;
+    decltype(&spr_text_names) text_names = nullptr;  // -s alone asks for it
     decltype(&spb_build_from_text) build_from_text;
     decltype(&spb_build_stats) build_stats;
     decltype(&spb_build_copy) build_copy;
@@ -477,6 +483,9 @@ int build_main(int argc, char** argv) {
     parse_build_options(argc, argv, &opts);
     if (opts.is_general_text)
         fatal_error("general-text input (-g) is not supported by this build: index FASTA files (-r / -i).");
+    if (opts.seq_table && opts.use_minimizers)
+        fatal_error("the sequence table (-s) cannot be written for a digested text (-m, -t or the default digestion):\n"
+                    "       digested coordinates cannot be turned back into bases. Build with -n.");
     opts.validate();
     if (opts.use_promotions) opts.use_dna_letters = false;
     const int digest_kind = !opts.use_minimizers ? 0 : opts.use_promotions ? SPX_DIGEST_PROMOTED : SPX_DIGEST_DNA;
@@ -489,7 +498,8 @@ int build_main(int argc, char** argv) {
     const std::string null_read_file = prefix_dir + "/spumoni_null_reads.fa";
 
     // everything the build needs of the library, before any file is written
-    const DeviceBuilder dev = resolve_builder();
+    DeviceBuilder dev = resolve_builder();
+    if (opts.seq_table) resolve(dev.text_names, "spr_text_names");
     if (spx_device_count() <= 0)
         fatal_error("no usable gfx950 device: `spumoni build` runs on the GPU and has no CPU fallback.");
     int device = 0;
@@ -560,6 +570,8 @@ int build_main(int argc, char** argv) {
     std::vector<uint8_t> text, fwd;
     std::vector<uint64_t> file_len(files.size()), seq_ends;
     std::vector<uint32_t> seq_file;
+    std::vector<uint8_t> names;
+    std::vector<uint64_t> name_ends;
     {
         HostBytes buf(total);
         for (size_t i = 0; i < files.size(); ++i) {
@@ -591,6 +603,13 @@ int build_main(int argc, char** argv) {
         seq_ends.resize(n_seqs);
         seq_file.resize(n_seqs);
         dev.text_copy(t, text.data(), file_len.data(), fwd.data(), seq_ends.data(), seq_file.data());
+        if (opts.seq_table) {
+            uint64_t n_name_bytes = 0;
+            dev.text_names(t, nullptr, nullptr, &n_name_bytes);
+            names.resize(n_name_bytes);
+            name_ends.resize(n_seqs);
+            dev.text_names(t, names.data(), name_ends.data(), nullptr);
+        }
         dev.text_free(t);
     }
     if (n_text == 0) {
@@ -672,6 +691,28 @@ int build_main(int argc, char** argv) {
         for (size_t i = 0; i < doc_lengths.size(); ++i)
             f += "group_" + std::to_string(i + 1) + "\t" + std::to_string(doc_lengths[i]) + "\n";
         write_bytes(prefix + ".fdi", f.data(), f.size());
+    }
+    if (opts.seq_table) {
+        // spumoni_amd/map.py: seq_table_bytes.  Without digestion the text is every sequence followed at once by its
+        // reverse complement (unless -c): a sequence's forward piece starts where the pieces before it end
+        const uint64_t strands = opts.use_rev_comp ? 2 : 1;
+        std::string f;
+        std::set<std::string> seen;
+        uint64_t start = 0, dup = 0;
+        for (uint64_t q = 0; q < n_seqs; ++q) {
+            const uint64_t len = seq_ends[q] - (q ? seq_ends[q - 1] : 0), n0 = q ? name_ends[q - 1] : 0;
+            const std::string name(reinterpret_cast<const char*>(names.data()) + n0, name_ends[q] - n0);
+            dup += !seen.insert(name).second;
+            f += name + "\t" + std::to_string(len) + "\t" + std::to_string(start) + "\t" + std::to_string(strands) + "\n";
+            start += len * strands;
+        }
+        if (start != n_text)
+            fatal_error("internal: the sequences of the table add up to %llu characters, the text has %llu.",
+                        (unsigned long long)start, (unsigned long long)n_text);
+        write_bytes(prefix + ".seqs", f.data(), f.size());
+        if (dup)
+            std::fprintf(stderr, "\nwarning: %llu sequence name(s) occur more than once in the sequence table\n",
+                         (unsigned long long)dup);
     }
     DONE_LOG((std::chrono::system_clock::now() - task_start));
 

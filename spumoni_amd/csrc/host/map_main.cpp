@@ -1,0 +1,238 @@
+// map_main.cpp -- `spumoni map`: one line of PAF per mapped read -- `spumoni extend`'s alignment in the coordinates of the
+// sequence it lies on: which sequence, which strand, where in it, cut at the sequence's borders, and on the reverse strand
+// turned round so that the CIGAR runs along the forward sequence (include/spumoni_map.h has the rule).  The sequences'
+// names, lengths and strands come from <prefix>.fa.seqs, the table `spumoni build -s` writes; the reads from reads.cpp
+// (same ids, same FASTA / FASTQ quirks as `run`), the MS index through the loaders `run` uses, and super-batches of
+// SPUMONI_SUPER_BATCH characters go through spn_map_begin / spn_map_fetch in calls of one piece each.  The driver is
+// read_command.cpp; a run that fails leaves no file.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "../../../include/spumoni_map.h"
+#include "read_command.hpp"
+
+using namespace spumoni_host;
+
+namespace {
+
+int spumoni_map_usage() {
+    std::fprintf(stderr, "spumoni map - Uses a spumoni MS index and its sequence table to map each read: the extended alignment of `spumoni extend` by sequence name, strand and position in the sequence, as PAF.\n");
+    std::fprintf(stderr, "Usage: spumoni map [options]\n\n");
+    std::fprintf(stderr, "Options:\n");
+    std::fprintf(stderr, "\t%-35sprints this usage message\n", "-h, --help");
+    std::fprintf(stderr, "\t%-25s%-10soutput prefix used for index; <prefix>.fa.seqs must exist (spumoni build -n -s)\n", "-r, --ref", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10spath to patterns file that will be used.\n", "-p, --pattern", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10sno minimizer digestion of reads: required, digested coordinates cannot be turned back into bases\n", "-n, --no-digest", "");
+    std::fprintf(stderr, "\t%-25s%-10srefused by `spumoni map`\n", "-m, --minimizer-alphabet", "");
+    std::fprintf(stderr, "\t%-25s%-10srefused by `spumoni map`\n", "-a, --dna-minimizer", "");
+    std::fprintf(stderr, "\t%-25s%-10ssmall window size (k) for finding minimizers (default: 4)\n", "-K, --small-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10slarge window size (w) for finding minimizers (default: 11)\n", "-W, --large-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10suse document array: matches chain within one document, and the dc tag names it\n", "-d, --doc-array", "");
+    std::fprintf(stderr, "\t%-25s%-10sa match is an anchor when it is at least this long, 1 or more (default: the\n", "-L, --min-length", "[INT]");
+    std::fprintf(stderr, "\t%-35sMS threshold `run -c` classifies with, from the null database)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest distance between two chained anchors in the read and in the text,\n", "-S, --max-dist", "[INT]");
+    std::fprintf(stderr, "\t%-35s1 .. 2147483647 (default: 5000)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest difference of those two distances, 0 .. 2147483647 (default: 500)\n", "-G, --max-gap", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat a unit of that difference costs, 0 .. 65535 (default: 1)\n", "-B, --gap-penalty", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10spredecessors an anchor looks back at, 1 .. 64 (default: 64)\n", "-H, --lookback", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10sa gap between two anchors is filled when neither side is longer, 1 .. 4096\n", "-F, --max-fill", "[INT]");
+    std::fprintf(stderr, "\t%-35s(default: 512)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10slargest end side that is extended, 1 .. 4096 (default: 512)\n", "-E, --max-extend", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10show far an extension may drift off the diagonal, 0 .. 63 (default: 16)\n", "-O, --band", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat an unequal column of an extension costs, 0 .. 65535 (default: 4)\n", "-N, --mismatch", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10swhat an inserted or deleted character of an extension costs, 0 .. 65535\n", "-I, --indel", "[INT]");
+    std::fprintf(stderr, "\t%-35s(default: 6); an equal column scores 1\n\n", "");
+    std::fprintf(stderr, "Matching statistics (-M) are implied. Writes <pattern>.paf, one line per mapped read (a read without a mapping has\n");
+    std::fprintf(stderr, "no line; their number is printed): id, length, read_start, read_end, strand (+ or -), sequence name, sequence\n");
+    std::fprintf(stderr, "length, target_start, target_end, matches, block length and 255 for the mapping quality (one chain per read: none\n");
+    std::fprintf(stderr, "is estimated), then NM:i: the edits (X + I + D), an:i: the anchors, ct:i: 1 when the alignment was cut at a sequence\n");
+    std::fprintf(stderr, "border on the left in text order, 2 on the right, 3 both, dc:i: the document under -d, and cg:Z: the CIGAR\n");
+    std::fprintf(stderr, "(= X I D N) along the sequence's forward strand. read_start and read_end are in the read as given, on either strand.\n\n");
+    return 1;
+}
+
+struct SeqTable {
+    std::vector<std::string> names;
+    std::vector<uint64_t> lengths;
+    uint32_t strands = 0;
+};
+
+// name<TAB>length<TAB>text_start<TAB>strands per line (spumoni_amd/map.py: read_seq_table)
+SeqTable read_seq_table(const std::string& path) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) fatal_error("cannot read %s", path.c_str());
+    SeqTable t;
+    std::string line;
+    uint64_t start = 0, lineno = 0;
+    while (std::getline(in, line)) {
+        ++lineno;
+        if (line.empty()) continue;
+        std::vector<std::string> f;
+        for (size_t at = 0;;) {
+            const size_t tab = line.find('\t', at);
+            f.push_back(line.substr(at, tab == std::string::npos ? tab : tab - at));
+            if (tab == std::string::npos) break;
+            at = tab + 1;
+        }
+        bool ok = f.size() == 4 && !f[0].empty();
+        unsigned long long v[3] = {0, 0, 0};
+        for (int i = 0; ok && i < 3; ++i) {
+            const std::string& s = f[i + 1];
+            ok = !s.empty() && s.size() <= 19 && s.find_first_not_of("0123456789") == std::string::npos;
+            if (ok) v[i] = std::strtoull(s.c_str(), nullptr, 10);
+        }
+        if (!ok) fatal_error("%s: line %llu is not name<TAB>length<TAB>text_start<TAB>strands", path.c_str(), (unsigned long long)lineno);
+        if (v[2] < 1 || v[2] > 2 || (t.strands && v[2] != t.strands) || v[0] == 0 || v[1] != start)
+            fatal_error("%s: line %llu: strands, length or text_start do not fit the lines before it", path.c_str(),
+                        (unsigned long long)lineno);
+        t.strands = (uint32_t)v[2];
+        t.names.push_back(f[0]);
+        t.lengths.push_back(v[0]);
+        start += v[0] * v[2];
+    }
+    if (t.names.empty()) fatal_error("%s: no sequences", path.c_str());
+    return t;
+}
+
+}  // namespace
+
+int map_main(int argc, char** argv) {
+    if (argc == 1) return spumoni_map_usage();
+    ReadOptions o;
+    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
+    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6;
+    parse_read_options(argc, argv, o, spumoni_map_usage, true, "L:S:G:B:H:F:E:O:N:I:",
+                       {{"min-length", required_argument, NULL, 'L'},
+                        {"max-dist", required_argument, NULL, 'S'},
+                        {"max-gap", required_argument, NULL, 'G'},
+                        {"gap-penalty", required_argument, NULL, 'B'},
+                        {"lookback", required_argument, NULL, 'H'},
+                        {"max-fill", required_argument, NULL, 'F'},
+                        {"max-extend", required_argument, NULL, 'E'},
+                        {"band", required_argument, NULL, 'O'},
+                        {"mismatch", required_argument, NULL, 'N'},
+                        {"indel", required_argument, NULL, 'I'}},
+                       [&](int c, const char* arg) {
+                           if (c == 'L') {
+                               o.have_threshold = true;
+                               o.threshold = std::strtoull(arg, nullptr, 10);
+                           } else {
+                               (c == 'S'   ? max_dist
+                                : c == 'G' ? max_gap
+                                : c == 'B' ? gap_penalty
+                                : c == 'H' ? lookback
+                                : c == 'F' ? max_fill
+                                : c == 'E' ? max_extend
+                                : c == 'O' ? band
+                                : c == 'N' ? mismatch
+                                           : indel) = arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
+                           }
+                       });
+    require_ref_and_pattern(o);
+    if (o.pml_requested)
+        fatal_warning("-P cannot be used with `spumoni map`: the anchors are read off matching statistics (-M is implied); "
+                      "PMLs have no pointers.");
+    if (o.use_promotions || o.use_dna_letters)
+        fatal_warning("-m / -a cannot be used with `spumoni map`: digested coordinates cannot be turned back into bases. "
+                      "Map against an index built with -n -s.");
+    if (o.min_digest)
+        fatal_warning("`spumoni map` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
+    o.ms = true;
+    validate_read_options(o);
+    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
+    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
+    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
+    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
+    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
+    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
+    if (max_extend < 1 || max_extend > 4096) fatal_warning("the largest extended end (-E) must be between 1 and 4096.");
+    if (band > 63) fatal_warning("the band (-O) must be between 0 and 63.");
+    if (mismatch > 65535) fatal_warning("the mismatch cost (-N) must be between 0 and 65535.");
+    if (indel > 65535) fatal_warning("the indel cost (-I) must be between 0 and 65535.");
+    o.ref_file += ".fa";
+    const std::string table_path = o.ref_file + ".seqs";
+    if (!is_file(table_path))
+        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", table_path.c_str());
+    const SeqTable table = read_seq_table(table_path);
+    const std::vector<void*> entry =
+        device_entry_points("map", {"spn_set_sequences", "spn_map_begin", "spn_map_fetch"}, "the map kernels");
+    auto set_sequences = reinterpret_cast<decltype(&spn_set_sequences)>(entry[0]);
+    auto map_begin = reinterpret_cast<decltype(&spn_map_begin)>(entry[1]);
+    auto map_fetch = reinterpret_cast<decltype(&spn_map_fetch)>(entry[2]);
+    ReadRun run;
+    open_read_run(o, 8u << 20, run);
+    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spn_map_begin)
+    if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
+        fatal_error("%s: %s", table_path.c_str(), spx_last_error());
+    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
+    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
+    const spa_params fill{(uint32_t)max_fill};
+    const spe_params ends{(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel};
+    std::fprintf(stderr, "[map] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); a match is an anchor from length %llu on "
+                 "(max-dist %llu, max-gap %llu, gap penalty %llu, lookback %llu, max-fill %llu, max-extend %llu, band %llu, mismatch %llu, "
+                 "indel %llu)\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
+                 (unsigned long long)min_length, max_dist, max_gap, gap_penalty, lookback, max_fill, max_extend, band, mismatch, indel);
+
+    LinesFile out;
+    out.open(o.pattern_file + ".paf", false);
+    uint64_t num_reads = 0, num_mapped = 0, num_cut = 0, num_reverse = 0;
+    std::vector<spn_mapping> maps;
+    std::vector<spa_alignment> recs;
+    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
+    std::vector<uint32_t> ops;
+    static const char op_char[16] = {'?', 'I', 'D', 'N', 'S', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    scan_reads(
+        run, out,
+        [&](ReadBatch& b) {
+            maps.resize(b.take + 1);
+            recs.resize(b.take + 1);
+            op_offs.assign(b.take + 1, 0);
+            ops.clear();
+            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
+            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
+                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+                uint64_t n = 0;
+                if (map_begin(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
+                              o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0, recs.data() + q0, &n) != SPX_OK)
+                    fatal_error("%s", spx_last_error());
+                const size_t at = ops.size();
+                ops.resize(at + n + 1);
+                piece_offs.resize(q1 - q0 + 1);
+                if (map_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
+                ops.resize(at + n);
+                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
+                // (without digestion a read's values are its characters)
+                for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
+            }
+        },
+        [&](const ReadBatch& b, size_t i) {
+            num_reads++;
+            const spn_mapping& m = maps[i];
+            if (m.seq == SPN_UNMAPPED) return;
+            const spa_alignment& c = recs[i];
+            std::fwrite(b.recs[i].id, 1, b.recs[i].id_len, out.f);
+            std::fprintf(out.f, "\t%llu\t%u\t%u\t%c\t%s\t%llu\t%llu\t%llu\t%u\t%u\t255\tNM:i:%u\tan:i:%u\tct:i:%u",
+                         (unsigned long long)b.values[i], m.read_start, m.read_end, m.strand ? '-' : '+', table.names[m.seq].c_str(),
+                         (unsigned long long)table.lengths[m.seq], (unsigned long long)m.target_start, (unsigned long long)m.target_end,
+                         m.matches, m.block, m.edits, c.anchors, m.cut);
+            if (o.use_doc) std::fprintf(out.f, "\tdc:i:%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
+            std::fputs("\tcg:Z:", out.f);
+            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e)
+                if ((ops[e] & 15) != SPE_OP_S) std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
+            std::fputc('\n', out.f);
+            num_mapped++;
+            num_cut += m.cut != 0;
+            num_reverse += m.strand;
+        });
+    std::fprintf(stderr, "[map] %llu reads, %llu mapped, %llu without a mapping, %llu cut at a sequence border, %llu on the reverse strand "
+                 "(%.3f sec). results are saved in *.paf\n",
+                 (unsigned long long)num_reads, (unsigned long long)num_mapped, (unsigned long long)(num_reads - num_mapped),
+                 (unsigned long long)num_cut, (unsigned long long)num_reverse,
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count());
+    return 0;
+}

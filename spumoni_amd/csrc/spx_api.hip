@@ -183,6 +183,7 @@ void spx_index_free(spx_index* ix) {
     release_align(ix);
     release_cigar(ix);
     release_extend(ix);
+    release_map(ix);
     if (ix->ev_dig) (void)hipEventDestroy(ix->ev_dig);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);

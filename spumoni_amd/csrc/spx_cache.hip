@@ -406,7 +406,8 @@ spx_index* spx_index_clone(spx_index* src, int device) {
         ix->force_lanes_per_wave = src->force_lanes_per_wave;
         ix->force_digest_kernel = src->force_digest_kernel;
         ix->digest_parked = src->digest_parked;
-        return rc;
+        if (rc != SPX_OK) return rc;
+        return clone_map(src, ix);  // (the sequence table is the handle's own, not one of the shared arrays)
     };
     if (body() != SPX_OK) {
         spx_index_free(ix);

@@ -341,6 +341,24 @@ struct spx_index {
     uint64_t extend_extra[8] = {};
     bool extend_ready = false;
     uint64_t extend_ready_n = 0, extend_ready_reads = 0;
+    // mappings (spx_map.hip): the piece starts P[0 .. map_pieces] on the device beside the index -- this handle's own
+    // copy, a clone has another -- and the lengths they came from; each read's plan, entry count and the scan's space
+    // (under mu), then spn_map_begin's read offsets, records, op offsets and entries (under host_mu); the event between
+    // the two steps of the last call and their times; what that call counted (reads, mapped, cut, reverse, entries in
+    // and out, characters cut, error bits); and the entries that wait for spn_map_fetch
+    uint64_t* map_P = nullptr;
+    uint64_t map_pieces = 0;
+    uint32_t map_strands = 0;
+    std::vector<uint64_t> map_seq_lengths;
+    enum { N_PLAN, N_OCNT, N_CUB, N_ROFFS, N_OUT, N_OOFFS, N_OPS, N_COUNT };
+    Scratch map_scr[N_COUNT];
+    Product map;  // (acc unused: map_acc)
+    hipEvent_t ev_map = nullptr;
+    bool map_steps = false;
+    float map_step_ms[2] = {};
+    uint64_t map_acc[8] = {};
+    bool map_ready = false;
+    uint64_t map_ready_n = 0, map_ready_reads = 0;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -478,6 +496,9 @@ void release_align(spx_index* ix);
 void release_cigar(spx_index* ix);
 // spx_extend.hip: the same for the extended CIGARs
 void release_extend(spx_index* ix);
+// spx_map.hip: the same for the mappings and the sequence table; and the table of `src` copied into a fresh clone
+void release_map(spx_index* ix);
+int clone_map(spx_index* src, spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on

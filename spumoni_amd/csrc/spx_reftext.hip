@@ -32,6 +32,8 @@ struct spr_text {
     std::vector<uint8_t> text, fwd;
     std::vector<uint64_t> file_len, seq_ends;
     std::vector<uint32_t> seq_file;
+    std::vector<uint8_t> names;       // the sequences' names back to back (spr_text_names)
+    std::vector<uint64_t> name_ends;  // their cumulative ends
 };
 
 namespace spx {
@@ -425,6 +427,48 @@ void refuse_byte(const uint8_t* bytes, const uint64_t* file_ends, uint32_t n_fil
               f, name.c_str(), (unsigned)bytes[pos], (unsigned long long)(pos - start));
 }
 
+// The names of the sequences that kept a byte, in the order of the parse, from the host's copy of the input (one memchr
+// per line; a sequence line is looked at until its first kept byte): a header's bytes behind '>' up to the first ASCII
+// whitespace; seq<k>, k the sequence's 1-based ordinal over all files, for an empty name and for the lines before a
+// file's first header.  The line rules are the parse's: a line ends at '\n', a line whose first byte is '>' is a header,
+// a file's start and end delimit like a header, a sequence keeps a byte when one of its lines has a non-blank byte.
+void sequence_names(spr_text& R, const uint8_t* bytes, const uint64_t* file_ends, uint32_t n_files) {
+    auto is_blank = [](uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); };
+    uint64_t ordinal = 0;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const uint64_t end = file_ends[f];
+        uint64_t pos = f ? file_ends[f - 1] : 0, h0 = 0, h1 = 0;  // [h0, h1): the open sequence's header behind '>'
+        bool kept = false;
+        auto close = [&]() {
+            if (!kept) return;
+            ++ordinal;
+            uint64_t e = h0;
+            while (e < h1 && !is_blank(bytes[e])) ++e;
+            if (e > h0) {
+                R.names.insert(R.names.end(), bytes + h0, bytes + e);
+            } else {
+                const std::string name = "seq" + std::to_string(ordinal);
+                R.names.insert(R.names.end(), name.begin(), name.end());
+            }
+            R.name_ends.push_back(R.names.size());
+        };
+        while (pos < end) {
+            const uint8_t* nl = (const uint8_t*)memchr(bytes + pos, '\n', end - pos);
+            const uint64_t le = nl ? (uint64_t)(nl - bytes) : end;
+            if (bytes[pos] == '>') {
+                close();
+                h0 = pos + 1;
+                h1 = le;
+                kept = false;
+            } else if (!kept) {
+                for (uint64_t i = pos; i < le && !kept; ++i) kept = !is_blank(bytes[i]);
+            }
+            pos = le + 1;
+        }
+        close();
+    }
+}
+
 int too_long(uint64_t n_text, uint64_t max_text) {
     set_error("the text has %llu characters, more than max_text (%llu)", (unsigned long long)n_text,
               (unsigned long long)max_text);
@@ -685,6 +729,19 @@ spr_text* spr_text_from_fasta(const uint8_t* bytes, uint64_t n_bytes, const uint
         set_error("out of host memory");
         rc = SPX_E_ARG;
     }
+    if (rc == SPX_OK) {
+        try {
+            sequence_names(*t, bytes, file_ends, n_files);
+        } catch (const std::bad_alloc&) {
+            set_error("out of host memory");
+            rc = SPX_E_ARG;
+        }
+        if (rc == SPX_OK && t->name_ends.size() != t->seq_file.size()) {
+            set_error("internal: the headers name %llu sequences, the parse found %llu", (unsigned long long)t->name_ends.size(),
+                      (unsigned long long)t->seq_file.size());
+            rc = SPX_E_FORMAT;
+        }
+    }
     if (rc != SPX_OK) {
         delete t;
         return nullptr;
@@ -714,6 +771,17 @@ int spr_text_copy(const spr_text* t, uint8_t* text, uint64_t* file_text_lengths,
     if (fwd && !t->fwd.empty()) memcpy(fwd, t->fwd.data(), t->fwd.size());
     if (seq_ends && !t->seq_ends.empty()) memcpy(seq_ends, t->seq_ends.data(), 8 * t->seq_ends.size());
     if (seq_file && !t->seq_file.empty()) memcpy(seq_file, t->seq_file.data(), 4 * t->seq_file.size());
+    return SPX_OK;
+}
+
+int spr_text_names(const spr_text* t, uint8_t* names, uint64_t* name_ends, uint64_t* n_name_bytes) {
+    if (!t) {
+        set_error("text is null");
+        return SPX_E_ARG;
+    }
+    if (names && !t->names.empty()) memcpy(names, t->names.data(), t->names.size());
+    if (name_ends && !t->name_ends.empty()) memcpy(name_ends, t->name_ends.data(), 8 * t->name_ends.size());
+    if (n_name_bytes) *n_name_bytes = t->names.size();
     return SPX_OK;
 }
 
