@@ -1172,6 +1172,20 @@ int launch_lanes(spx_index* ix, const BatchArgs& args, hipStream_t stream, uint6
     // such launch, a later one (the pieces of a pipelined host batch) zeroes it again, in stream order.
     const bool dynamic = fast && CHUNK == 0 && ix->force_lanes_per_wave == 0 && !small_batch && items > grid * WALK_TPB;
     if (dynamic) {
+        // the instance that deals on demand is another kernel: with its claim-staged output (spx_walk_fast.inc, STAGE) it holds
+        // 37.6 KB of LDS a block where the strided one holds 12, so fewer of its blocks may fit a CU ("waves_per_cu" 20: four
+        // blocks, not five).  A block that is not resident starts when another ends -- with its strided first round still to
+        // do, long after the claimed part began -- so the launch is sized by this instance's own occupancy.
+        const int dslot = MODE * 2 + (DOC ? 1 : 0);
+        if (ix->occ_blocks_dyn[dslot] == 0) {
+            int occ_d = 0;
+            SPX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_d, k_walk_fast<MODE, DOC, NARROW, 0, false, true>, WALK_TPB, 0));
+            ix->occ_blocks_dyn[dslot] = occ_d < 1 ? 1 : occ_d;
+        }
+        if (ix->occ_blocks_dyn[dslot] < occ) {
+            occ = ix->occ_blocks_dyn[dslot];
+            grid = (uint64_t)occ * ix->num_cus;  // (fewer lanes: the batch still has more reads than lanes)
+        }
         a.claim = &ix->counters->claim;
         if (ix->claim_used) SPX_HIP(hipMemsetAsync(a.claim, 0, sizeof(unsigned long long), stream));
         ix->claim_used = true;

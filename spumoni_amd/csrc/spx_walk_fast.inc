@@ -93,10 +93,27 @@ __device__ __forceinline__ void lf_target_ct(uint32_t LFrun, uint32_t LFoff, uin
 // waits for the atomic alone.  Reads cost unequally (one that matches takes ~35 iterations, a random one ~48): under
 // striding a lane's total is a draw, a wavefront runs as long as its slowest lane and the launch as long as its slowest
 // wavefront (DESIGN.md 4.1, profiles/mix_penalty_before.txt).  Which lane walks which read is not observable.
+// How the results leave (PML).  Everywhere but below: when a lane has the reset bits of 64 characters (or its read ends) the
+// wavefront writes that stretch, one store per word.  For short reads that is one store per read, of a stretch that neither
+// starts nor ends on a line's boundary, while the reads beside it -- same claim, other lanes -- end tens of iterations
+// later: every line of the output goes to memory two or three times, in pieces (profiles/claim_output_ab.txt).
+// STAGE (DYN, PML, no document ids): a wavefront's reads come in claims of 64 consecutive indices (the first round,
+// wave * 64 + lane, is one too), so a claim's lengths are one contiguous stretch of the output and its class records one
+// aligned KB.  A claim takes one of the wavefront's CSLOTS slots in LDS when its first read is handed out; a read of up to 64
+// characters leaves its one word of reset bits and its class record there when it ends; when the claim's last read has
+// ended -- counted on wave-uniform values, once per iteration -- the wavefront writes the stretch in whole aligned lines
+// (the first and the last masked to the stretch) and the records as one store.  Lane l takes value l of each line and finds
+// the read it belongs to through a bit map of the reads' first positions (stretches of up to 64 lines: every claim of reads
+// that fit a word) or, behind it, with a cursor over the reads' bases.  What does not fit keeps the path above,
+// unchanged and correct on its own: a read of more than 64 characters (all its words, and its record), an empty read (its
+// record; both are only counted as ended), and every read of a claim that found no slot free.  The loop's exit needs
+// nothing new: a lane is done only after its last read was counted, in the iteration that read ended in.
 template <int MODE, bool DOC, bool NARROW, int CHUNK = 0, bool EARLY = false, bool DYN = false>
 __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const BatchArgs b) {
     constexpr bool AUX = (MODE == SPX_MODE_MS) || DOC;  // per-jump side data (samples / doc ids)
     constexpr bool PML = MODE == SPX_MODE_PML;
+    // claim-staged output (see "How the results leave" above): the dynamic deal's PML walk without document ids
+    constexpr bool STAGE = DYN && PML && !DOC;
     if (CHUNK == 2 && b.ch.round > 1 && b.ch.pending[b.ch.round] == 0) return;  // no seam was left open
     __shared__ HotLetter s_hot[256];
     // MS pointers (and, with them, the document ids) wait in LDS until the sixteen that share an aligned 128-byte line of
@@ -117,6 +134,17 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     __shared__ uint16_t s_docs[DSTAGE ? WALK_TPB * DROW : 1];
     const LetterInfo* const s_let = ix.letters;  // (the full letter records are only read on rare paths: from memory)
     __shared__ uint32_t s_win[8 * WALK_TPB];
+    // STAGE: CSLOTS claims per wavefront wait here until their last read has ended.  Per read of a claim: where its
+    // results go (written when the read is taken), and -- written when it ends, if it is no longer than one word -- its
+    // reset bits, its length (0: not staged -- empty, longer than a word, or not ended) and its class record.
+    // Wave-private like s_ptrs: the LDS serves a wavefront's accesses in order, nothing is shared between wavefronts.
+    // 2112 bytes a claim, 25 344 a block at three claims a wavefront: 37.6 KB with the tables above, four blocks a CU.
+    constexpr int CSLOTS = 3, CWAVE = CSLOTS * 64, CALL = (WALK_TPB / 64) * CWAVE;
+    constexpr uint32_t C_NONE = 0xffffffffu;
+    __shared__ uint64_t s_cbase[STAGE ? CALL : 1];
+    __shared__ uint64_t s_cword[STAGE ? CALL : 1];
+    __shared__ uint64_t s_ccls[STAGE ? 2 * CALL : 1];  // spx_class: sum_max, above | below << 32
+    __shared__ uint8_t s_clen[STAGE ? CALL : 1];
     const char* const rows_b = reinterpret_cast<const char*>(ix.rows);
     const char* const fat_b = reinterpret_cast<const char*>(ix.fat);
     const uint32_t fs = ix.fat_stride;
@@ -164,6 +192,39 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     uint32_t rd = (uint32_t)((((uint64_t)blockIdx.x * blockDim.x + tid) >> 6) * lpw) + (tid & 63);
     uint32_t ph = (rd < nitems && (tid & 63) < lpw) ? Q_READ : Q_DONE;
     const char* addr = ph == Q_READ ? item_b + (uint64_t)rd * ITEM_BYTES : item_b;
+    // STAGE.  Per lane: cidx, where its read stands in the wavefront's staging area (slot * 64 + index in the claim;
+    // C_NONE: the read's claim found no slot, or the read has been counted as ended).  Per wavefront, in scalar
+    // registers: per slot the claim's first read, its size (0: the slot is free) and how many of its reads have not
+    // ended; per range of the reservoir, what turns a read index of it into a cidx (w_cv: its claim has a slot).
+    const uint32_t cw0 = (tid >> 6) * CWAVE;
+    uint32_t cidx = C_NONE;
+    uint32_t c_first[CSLOTS] = {0, 0, 0}, c_n[CSLOTS] = {0, 0, 0}, c_left[CSLOTS] = {0, 0, 0};
+    uint32_t w_cb0 = 0, w_cb1 = 0;
+    bool w_cv0 = false, w_cv1 = false, w_ct0 = false, w_ct1 = false;  // (w_ct: the range's claim has asked for a slot)
+    // a claim of `count` reads from `first` on takes a free slot; when there is none its reads go out one by one, as ever
+    auto take_slot = [&](uint32_t first, uint32_t count, uint32_t& cb, bool& cv) {
+        const uint32_t fs_ = c_n[0] == 0 ? 0u : (c_n[1] == 0 ? 1u : (c_n[2] == 0 ? 2u : 3u));
+        cv = fs_ < (uint32_t)CSLOTS;
+        if (cv) {
+#pragma unroll
+            for (int s = 0; s < CSLOTS; ++s) {
+                c_first[s] = fs_ == (uint32_t)s ? first : c_first[s];
+                c_n[s] = fs_ == (uint32_t)s ? count : c_n[s];
+                c_left[s] = fs_ == (uint32_t)s ? count : c_left[s];
+            }
+            cb = fs_ * 64 - first;
+            s_clen[cw0 + fs_ * 64 + (threadIdx.x & 63)] = 0;
+        }
+    };
+    static_assert(CSLOTS == 3, "the slots' scalars are written out by hand");
+    if (STAGE) {
+        // the first round is a claim too: reads [wave * 64, wave * 64 + 64), clipped to the batch, in slot 0
+        const uint32_t f0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rd - (tid & 63)));
+        c_first[0] = f0;
+        c_n[0] = c_left[0] = f0 < nitems ? (nitems - f0 < 64u ? nitems - f0 : 64u) : 0u;
+        cidx = ph == Q_READ ? (tid & 63) : C_NONE;
+        s_clen[cw0 + (tid & 63)] = 0;
+    }
     uint32_t seen = 0;  // chunked walk: what the steps of this chunk reset so far (bit 0 length / sample, bit 1 document id)
     uint64_t fb = 0;    // ... and the flag bytes of the aligned group of 8 characters being collected
     uint32_t fl = 0;          // F_*
@@ -349,6 +410,7 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 } else {
                     base = u64of(ga.x, ga.y);
                     m = (uint32_t)(u64of(ga.z, ga.w) - base);
+                    if (STAGE && cidx != C_NONE) s_cbase[cw0 + cidx] = base;  // (every read of a staged claim: the writer's map)
                 }
                 ibase = (CHUNK == 0 && b.in_starts != nullptr) ? side_in : base;
                 if (m == 0) {
@@ -613,6 +675,9 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 // the bit of character p ends up at position p & 63 when the word is written (at p & 63 == 0)
                 const uint32_t xi = x - 1;
                 x = xi;
+                // the read's results wait in LDS for the rest of its claim: it fits one word and its claim has a slot
+                const bool staged = STAGE && cidx != C_NONE && m <= 64;
+                (void)staged;
                 bool met = false;  // pass 2: the walk stands where the speculative walk of this chunk stood
                 if (CHUNK == 2) {
                     // pass 2 writes over the speculative results one value at a time (a few steps per chunk)
@@ -727,9 +792,14 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 if (PML && CHUNK != 2) {
                     mbits = (mbits << 1) | (length == 0 ? 1u : 0u);
                     if ((xi & 63) == 0) {  // (two consecutive characters: at most one word completes per iteration)
-                        fbits = mbits;
-                        fxi = xi;
-                        flush = true;
+                        if (STAGE && staged) {  // (the read's only word: xi == 0)
+                            s_cword[cw0 + cidx] = mbits;
+                            s_clen[cw0 + cidx] = (uint8_t)m;
+                        } else {
+                            fbits = mbits;
+                            fxi = xi;
+                            flush = true;
+                        }
                         mbits = 0;
                     }
                 }
@@ -747,7 +817,12 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 if (xi == 0 || (CHUNK == 2 && met)) {
                     if (want_class) {
                         const bool ab = bin_max >= b.max_value_thr;
-                        b.out_class[rd] = spx_class{sum_max + bin_max, above + (ab ? 1u : 0u), below + (ab ? 0u : 1u)};
+                        if (STAGE && staged) {
+                            s_ccls[2 * (cw0 + cidx)] = sum_max + bin_max;
+                            s_ccls[2 * (cw0 + cidx) + 1] = u64of(above + (ab ? 1u : 0u), below + (ab ? 0u : 1u));
+                        } else {
+                            b.out_class[rd] = spx_class{sum_max + bin_max, above + (ab ? 1u : 0u), below + (ab ? 0u : 1u)};
+                        }
                     }
                     rd += DYN ? 0u : nlanes;
                     ph = DYN ? Q_WANT : (rd < nitems ? Q_READ : Q_DONE);
@@ -775,6 +850,119 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
             addr = rows_b;
             fl &= ~(F_WIDE | F_EMB);
         }
+        if (STAGE) {
+            // ---- claims whose last read ended in this iteration leave (the bookkeeping on wave-uniform values) ----
+            // a lane that ended a read -- staged or not, empty ones too -- stands in Q_WANT with its cidx still set: it is
+            // counted once and gives the cidx up
+            const bool ended = ph == Q_WANT && cidx != C_NONE;
+            if (__builtin_amdgcn_ballot_w64(ended) != 0) {
+                uint32_t ready = 0;
+#pragma unroll
+                for (int s = 0; s < CSLOTS; ++s) {
+                    c_left[s] -= (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ended && (cidx >> 6) == (uint32_t)s));
+                    ready |= (c_n[s] != 0 && c_left[s] == 0) ? 1u << s : 0u;
+                }
+                cidx = ended ? C_NONE : cidx;
+                while (ready != 0) {
+                    const uint32_t s = (uint32_t)__builtin_ctz(ready);
+                    ready &= ready - 1;
+                    const uint32_t cn = s == 0 ? c_n[0] : (s == 1 ? c_n[1] : c_n[2]);
+                    const uint32_t cf = s == 0 ? c_first[0] : (s == 1 ? c_first[1] : c_first[2]);
+                    c_n[0] = s == 0 ? 0u : c_n[0];
+                    c_n[1] = s == 1 ? 0u : c_n[1];
+                    c_n[2] = s == 2 ? 0u : c_n[2];
+                    const uint32_t lane = tid & 63, so = cw0 + s * 64;
+                    // the class records: one contiguous, aligned stretch of 16 bytes a read
+                    if (want_class && lane < cn && s_clen[so + lane] != 0) {
+                        const uint64_t cv = s_ccls[2 * (so + lane) + 1];
+                        b.out_class[cf + lane] = spx_class{s_ccls[2 * (so + lane)], (uint32_t)cv, (uint32_t)(cv >> 32)};
+                    }
+                    if (want_len) {
+                        // The lengths: the claim's reads lie one after the other from position lo on.  The wavefront goes over
+                        // the aligned lines of 64 values (128 / 256 bytes, by address) that the stretch touches, lane l taking
+                        // value l of each line: it finds the read the position belongs to -- through a bit map when the stretch
+                        // is short enough for one, else with a cursor that only moves up (positions and bases both
+                        // ascend) -- and writes lengths[p] as the store loop below does -- the
+                        // distance to the first reset at or after p, the read's end when there is none.  A position whose
+                        // read was not staged (clen == 0: empty, or longer than a word and written by that loop), or that
+                        // lies outside the stretch (first and last line), fails `p < clen` and is left alone.
+                        const int64_t lo = (int64_t)s_cbase[so];
+                        const int64_t hi = (int64_t)s_cbase[so + cn - 1] + s_clen[so + cn - 1];
+                        const int64_t skew = (int64_t)(((uintptr_t)b.out_lengths >> (NARROW ? 1 : 2)) & 63);
+                        const int64_t e00 = ((lo + skew) & ~63ll) - skew;  // the first line's first position
+                        uint32_t ci = 0;
+                        int64_t cb = lo;
+                        if (hi - e00 <= 64 * 64) {
+                            // At most 64 lines (always, but for claims with reads longer than a word): the map from position to
+                            // read without a search.  The reads that hold positions move to the front of the slot (lane i has
+                            // read i in registers; an empty read would share its first position with the next one) and mark
+                            // that position in a bit map of the stretch, one word a line, in the slot's class records (which
+                            // have left).  Lane l keeps line l's word; per line the word is read from that lane, and position
+                            // q of the line belongs to read (marks before the line) + (marks of the line up to q) - 1.
+                            const bool mine = lane < cn;
+                            const int64_t bi = mine ? (int64_t)s_cbase[so + lane] : hi;
+                            const int64_t bn = lane + 1 < cn ? (int64_t)s_cbase[so + lane + 1] : hi;  // (the last read ends at hi, staged or not)
+                            const uint32_t li = s_clen[so + lane];
+                            const uint64_t wi = s_cword[so + lane];
+                            const bool holds = mine && bn > bi;
+                            const uint64_t hmask = __builtin_amdgcn_ballot_w64(holds);
+                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hmask, 0u));
+                            unsigned long long* const bits = reinterpret_cast<unsigned long long*>(&s_ccls[2 * so]);
+                            bits[lane] = 0;
+                            if (holds) {
+                                const uint32_t q = (uint32_t)(bi - e00);  // < 4096: bi < hi
+                                atomicOr(&bits[q >> 6], 1ull << (q & 63));
+                                s_cbase[so + rank] = (uint64_t)bi;
+                                s_clen[so + rank] = (uint8_t)li;
+                                s_cword[so + rank] = wi;
+                            }
+                            const uint64_t mown = atomicOr(&bits[lane], 0ull);
+                            const uint32_t nlines = (uint32_t)((hi - e00 + 63) >> 6);
+                            uint32_t before = 0;
+                            for (uint32_t ln = 0; ln < nlines; ++ln) {
+                                const uint64_t mk = u64of((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mown, (int)ln),
+                                                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mown >> 32), (int)ln));
+                                const uint32_t upto = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u)) +
+                                                      (uint32_t)((mk >> lane) & 1);
+                                before += (uint32_t)__popcll(mk);
+                                const int64_t e = e00 + (int64_t)ln * 64 + lane;
+                                if (upto != 0) {  // (0: in front of the claim's first position)
+                                    const uint64_t p = (uint64_t)(e - (int64_t)s_cbase[so + upto - 1]);
+                                    const uint32_t cm = s_clen[so + upto - 1];
+                                    if (p < cm) {
+                                        const uint64_t t = s_cword[so + upto - 1] >> p;
+                                        const uint32_t v = t != 0 ? (uint32_t)__builtin_ctzll(t) : cm - (uint32_t)p;
+                                        if (NARROW)
+                                            reinterpret_cast<uint16_t*>(b.out_lengths)[e] = (uint16_t)v;
+                                        else
+                                            b.out_lengths[e] = v;
+                                    }
+                                }
+                            }
+                        } else
+                        for (int64_t e0 = e00; e0 < hi; e0 += 64) {
+                            const int64_t e = e0 + lane;
+                            while (ci + 1 < cn) {
+                                const int64_t nb = (int64_t)s_cbase[so + ci + 1];
+                                if (nb > e) break;
+                                cb = nb;
+                                ++ci;
+                            }
+                            const uint64_t p = (uint64_t)(e - cb);
+                            const uint32_t cm = s_clen[so + ci];
+                            if (p < cm) {
+                                const uint64_t t = s_cword[so + ci] >> p;
+                                const uint32_t v = t != 0 ? (uint32_t)__builtin_ctzll(t) : cm - (uint32_t)p;
+                                if (NARROW)
+                                    reinterpret_cast<uint16_t*>(b.out_lengths)[e] = (uint16_t)v;
+                                else
+                                    b.out_lengths[e] = v;
+                            }
+                        }
+                    }
+                }
+            }
+        }
         if (DYN) {
             // ---- the dynamic deal (all of it on wave-uniform values) ----
             if (w_pend) {  // the claim that went out with this iteration's gather: reads [nlanes + claimed, ... + CHUNK_CLAIM)
@@ -785,11 +973,15 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 w_e1 = (uint32_t)(c1 < nitems ? c1 : nitems);
                 w_dry = c1 >= nitems;  // (the word only grows: a later claim would lie past the end)
                 w_pend = false;
+                w_cv1 = w_ct1 = false;
             }
             if (w_n0 == w_e0) {  // the first range is used up: the second takes its place
                 w_n0 = w_n1;
                 w_e0 = w_e1;
                 w_n1 = w_e1 = 0;
+                w_cb0 = w_cb1;
+                w_cv0 = w_cv1;
+                w_ct0 = w_ct1;
             }
             const uint64_t wants = __builtin_amdgcn_ballot_w64(ph == Q_WANT);
             if (wants != 0) {
@@ -798,11 +990,24 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                 const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(wants >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wants, 0u));
                 const uint32_t have0 = w_e0 - w_n0, have1 = w_e1 - w_n1, nw = (uint32_t)__popcll(wants);
                 const bool over = !w_pend && w_dry;
+                if (STAGE) {
+                    // a claim takes its slot when its first read is handed out (not when it arrives: it would hold the slot
+                    // for the iterations it waits in the reservoir)
+                    if (have0 != 0 && !w_ct0) {
+                        take_slot(w_n0, have0, w_cb0, w_cv0);
+                        w_ct0 = true;
+                    }
+                    if (nw > have0 && have1 != 0 && !w_ct1) {
+                        take_slot(w_n1, have1, w_cb1, w_cv1);
+                        w_ct1 = true;
+                    }
+                }
                 if (ph == Q_WANT) {
                     const bool got = j < have0 + have1;
                     rd = j < have0 ? w_n0 + j : w_n1 + (j - have0);
                     ph = got ? Q_READ : (over ? Q_DONE : Q_WANT);
                     addr = got ? item_b + (uint64_t)rd * ITEM_BYTES : rows_b;
+                    if (STAGE) cidx = (got && (j < have0 ? w_cv0 : w_cv1)) ? rd + (j < have0 ? w_cb0 : w_cb1) : C_NONE;
                 }
                 const uint32_t t0 = nw < have0 ? nw : have0, t1 = (nw - t0) < have1 ? (nw - t0) : have1;
                 w_n0 += t0;
@@ -812,6 +1017,9 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
                     w_n0 = w_n1;
                     w_e0 = w_e1;
                     w_n1 = w_e1 = 0;
+                    w_cb0 = w_cb1;
+                    w_cv0 = w_cv1;
+                    w_ct0 = w_ct1;
                 }
             }
             // refill ahead of need: the next iteration can take at most 64 reads (a lane ends one read per iteration)
@@ -998,6 +1206,8 @@ __global__ void __launch_bounds__(WALK_TPB) k_walk_fast(const DevIndex ix, const
     (void)ckb;
     (void)w_again;
     (void)w_n0, (void)w_e0, (void)w_n1, (void)w_e1, (void)w_pend, (void)w_dry, (void)w_wait, (void)claimed;
+    (void)cidx, (void)c_first, (void)c_n, (void)c_left, (void)w_cb0, (void)w_cb1, (void)w_cv0, (void)w_cv1, (void)w_ct0, (void)w_ct1;
+    (void)take_slot, (void)cw0, (void)s_cbase, (void)s_cword, (void)s_ccls, (void)s_clen;
     // every character of the batch is one step
     if (CHUNK != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&b.counters->steps, (unsigned long long)(b.offs[b.nreads] - b.offs[0]));
 }
