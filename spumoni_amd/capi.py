@@ -937,6 +937,106 @@ class Index:
         out["step_ms"] = list(s.step_ms)
         return out
 
+    # -- coverage (include/spumoni_cover.h) --------------------------------------------
+    def cover_add_device(self, d_mappings, d_op_offsets, d_ops, d_diff, d_mism, d_seq_counts, in_entries=None, stream=None) -> None:
+        """map_device's (d_out, d_out_op_offsets, d_out_ops) added to d_diff int32[G + 1], d_mism int32[G] and d_seq_counts
+        int64[2 * n_seqs] (cover.py).  in_entries defaults to d_ops' size."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_op_offsets.numel() - 1
+        if in_entries is None:
+            in_entries = d_ops.numel()
+        _check(_spd().spd_cover_add_device(self._h, _t_ptr(d_mappings), _t_ptr(d_op_offsets), _t_ptr(d_ops), int(in_entries), nreads,
+                                           _t_ptr(d_diff), _t_ptr(d_mism), _t_ptr(d_seq_counts), C.c_void_p(st.cuda_stream)))
+
+    def cover_finish_device(self, d_diff, d_mism, d_seq_counts, d_depth=None, d_out=None, stream=None):
+        """(d_depth int32[G], d_out int64 (n_seqs, 6), a view of cover.SEQ_COVER_DTYPE) of the three arrays, which stay as
+        they are."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if d_depth is None:
+            d_depth = torch.empty(d_mism.numel(), dtype=torch.int32, device=d_mism.device)
+        if d_out is None:
+            d_out = torch.empty((d_seq_counts.numel() // 2, 6), dtype=torch.int64, device=d_mism.device)
+        _check(_spd().spd_cover_finish_device(self._h, _t_ptr(d_diff), _t_ptr(d_mism), _t_ptr(d_seq_counts), _t_ptr(d_depth),
+                                              _t_ptr(d_out), C.c_void_p(st.cuda_stream)))
+        return d_depth, d_out
+
+    def cover_runs_device(self, d_depth, d_mism, min_depth, run_capacity, d_runs=None, d_count=None, stream=None):
+        """(d_runs int64 (run_capacity, 4), a view of cover.RUN_DTYPE; d_count int64[1]): the runs of depth >= min_depth."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if d_runs is None:
+            d_runs = torch.empty((max(int(run_capacity), 1), 4), dtype=torch.int64, device=d_depth.device)
+        if d_count is None:
+            d_count = torch.empty(1, dtype=torch.int64, device=d_depth.device)
+        _check(_spd().spd_cover_runs_device(self._h, _t_ptr(d_depth), _t_ptr(d_mism), int(min_depth), int(run_capacity), _t_ptr(d_runs),
+                                            _t_ptr(d_count), C.c_void_p(st.cuda_stream)))
+        return d_runs, d_count
+
+    def cover_reset(self) -> None:
+        """Allocates the handle's coverage arrays for the sequence table in force, or zeroes them."""
+        _check(_spd().spd_cover_reset(self._h))
+
+    def cover_add_host(self, seqs, offs, min_length, chain_params=None, params=None, extend_params=None, digest=None, want_docs=False):
+        """spd_cover_add_batch: map_host's arguments; the mappings are added to the handle's arrays on the device and come
+        back (map.MAPPING_DTYPE[reads]); the entries do not."""
+        from .align import AlignParams
+        from .chain import ChainParams
+        from .extend import ExtendParams
+        from .map import MAPPING_DTYPE
+
+        L = _spd()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        out = np.zeros(max(nreads, 1), dtype=MAPPING_DTYPE)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        ep = SpeParams(*(int(v) for v in (ExtendParams() if extend_params is None else extend_params)))
+        _check(L.spd_cover_add_batch(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                     C.byref(cp), C.byref(ap), C.byref(ep), _np_ptr(out)))
+        return out[:nreads]
+
+    def cover_summary(self, n_seqs: int) -> np.ndarray:
+        """cover.SEQ_COVER_DTYPE[n_seqs] of everything added since cover_reset, in table order."""
+        from .cover import SEQ_COVER_DTYPE
+
+        out = np.zeros(max(int(n_seqs), 1), dtype=SEQ_COVER_DTYPE)
+        _check(_spd().spd_cover_summary(self._h, _np_ptr(out), int(n_seqs)))
+        return out[:int(n_seqs)]
+
+    def cover_runs(self, min_depth: int = 1) -> np.ndarray:
+        """spd_cover_runs_begin + _fetch: cover.RUN_DTYPE[] of the runs of depth >= min_depth."""
+        from .cover import RUN_DTYPE
+
+        L = _spd()
+        n = C.c_uint64(0)
+        _check(L.spd_cover_runs_begin(self._h, int(min_depth), C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=RUN_DTYPE)
+        _check(L.spd_cover_runs_fetch(self._h, _np_ptr(out)))
+        return out[:n.value]
+
+    def cover_depth(self, first: int, count: int):
+        """(depth uint32[count], mism uint32[count]) of the positions [first, first + count) of the forward genome."""
+        depth, mism = np.zeros(max(int(count), 1), dtype=np.uint32), np.zeros(max(int(count), 1), dtype=np.uint32)
+        _check(_spd().spd_cover_depth(self._h, int(first), int(count), _np_ptr(depth), _np_ptr(mism)))
+        return depth[:int(count)], mism[:int(count)]
+
+    def cover_stats(self) -> dict:
+        """Of the most recent cover_* calls: the reads, the mapped, added and skipped ones, intervals and atomic adds of the
+        adds (since cover_reset for cover_add_host, of the last call for cover_add_device), the runs of the last runs
+        call, the error and overflow flags and the time of the last add, finish and runs step."""
+        s = SpdCoverStats()
+        _check(_spd().spd_last_cover_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpdCoverStats._fields_}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -1222,6 +1322,41 @@ def _spn() -> C.CDLL:
         L.spn_map_fetch.argtypes = [vp, vp, vp]
         L.spn_last_map_stats.argtypes = [vp, C.POINTER(SpnMapStats)]
         _SPN_READY = True
+    return L
+
+
+# ---- the coverage (include/spumoni_cover.h) ------------------------------------------------------------------------
+COVER_EXPORTS = ["spd_cover_add_device", "spd_cover_finish_device", "spd_cover_runs_device", "spd_cover_reset", "spd_cover_add_batch",
+                 "spd_cover_summary", "spd_cover_runs_begin", "spd_cover_runs_fetch", "spd_cover_depth", "spd_last_cover_stats"]
+_SPD_READY = False
+
+
+class SpdCoverStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("mapped", C.c_uint64), ("added", C.c_uint64), ("skipped", C.c_uint64),
+                ("intervals", C.c_uint64), ("atomics", C.c_uint64), ("runs", C.c_uint64), ("error", C.c_uint32),
+                ("overflow", C.c_uint32), ("kernel_ms", C.c_float), ("step_ms", C.c_float * 3)]
+
+
+def _spd() -> C.CDLL:
+    """The library with the spd_* argtypes set (on first use)."""
+    global _SPD_READY
+    L = _spn()
+    if not hasattr(L, "spd_cover_add_batch"):
+        raise SpxError(f"{LIB_PATH} has no coverage kernels (spd_cover_add_batch): there is no CPU fallback")
+    if not _SPD_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spd_cover_add_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp]
+        L.spd_cover_finish_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.spd_cover_runs_device.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp]
+        L.spd_cover_reset.argtypes = [vp]
+        L.spd_cover_add_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams),
+                                          C.POINTER(SpeParams), vp]
+        L.spd_cover_summary.argtypes = [vp, vp, u64]
+        L.spd_cover_runs_begin.argtypes = [vp, u32, C.POINTER(u64)]
+        L.spd_cover_runs_fetch.argtypes = [vp, vp]
+        L.spd_cover_depth.argtypes = [vp, u64, u64, vp, vp]
+        L.spd_last_cover_stats.argtypes = [vp, C.POINTER(SpdCoverStats)]
+        _SPD_READY = True
     return L
 
 

@@ -1,0 +1,211 @@
+// cover_main.cpp -- `spumoni cover`: per sequence of the index, how many reads map to it, how much of it they cover and how
+// deep -- `spumoni map`'s mappings accumulated on the device into per-base depth and mismatch counts
+// (include/spumoni_cover.h has the rule), and one line per sequence in place of one line per read.  The options, the
+// sequence table, the reads and the index are `map`'s; super-batches of SPUMONI_SUPER_BATCH characters go through
+// spd_cover_add_batch in calls of one piece each and add up.  The driver is read_command.cpp; both files are written when
+// everything has been fetched, so a run that fails leaves none.
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../../include/spumoni_cover.h"
+#include "read_command.hpp"
+
+using namespace spumoni_host;
+
+namespace {
+
+int spumoni_cover_usage() {
+    std::fprintf(stderr, "spumoni cover - Uses a spumoni MS index and its sequence table to map each read as `spumoni map` does, and reports per sequence how many reads map to it, how much of it they cover and how deep.\n");
+    std::fprintf(stderr, "Usage: spumoni cover [options]\n\n");
+    std::fprintf(stderr, "Options:\n");
+    std::fprintf(stderr, "\t%-35sprints this usage message\n", "-h, --help");
+    std::fprintf(stderr, "\t%-25s%-10soutput prefix used for index; <prefix>.fa.seqs must exist (spumoni build -n -s)\n", "-r, --ref", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10spath to patterns file that will be used.\n", "-p, --pattern", "[FILE]");
+    std::fprintf(stderr, "\t%-25s%-10sno minimizer digestion of reads: required, digested coordinates cannot be turned back into bases\n", "-n, --no-digest", "");
+    std::fprintf(stderr, "\t%-25s%-10srefused by `spumoni cover`\n", "-m, --minimizer-alphabet", "");
+    std::fprintf(stderr, "\t%-25s%-10srefused by `spumoni cover`\n", "-a, --dna-minimizer", "");
+    std::fprintf(stderr, "\t%-25s%-10ssmall window size (k) for finding minimizers (default: 4)\n", "-K, --small-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10slarge window size (w) for finding minimizers (default: 11)\n", "-W, --large-window", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10suse document array: matches chain within one document\n", "-d, --doc-array", "");
+    std::fprintf(stderr, "\t%-25s%-10salso writes <pattern>.bedgraph: the runs of equal depth\n", "-b, --bedgraph", "");
+    std::fprintf(stderr, "\t%-25s%-10sthe smallest depth of a run in the bedgraph, 0 .. 4294967295 (default: 1)\n", "-D, --min-depth", "[INT]");
+    std::fprintf(stderr, "\t%-25s%-10s`spumoni map`'s options with its defaults: the anchors' minimum length, the chain\n", "-L -S -G -B -H", "[INT]");
+    std::fprintf(stderr, "\t%-35s(max-dist, max-gap, gap-penalty, lookback)\n", "");
+    std::fprintf(stderr, "\t%-25s%-10s... the filled gaps (max-fill) and the extension (max-extend, band, mismatch, indel)\n\n", "-F -E -O -N -I", "[INT]");
+    std::fprintf(stderr, "Matching statistics (-M) are implied. Writes <pattern>.cover, one line per sequence in the table's order: name,\n");
+    std::fprintf(stderr, "length, reads mapped to it, covered bases, breadth (covered / length), bases (the sum of the depth), mean depth\n");
+    std::fprintf(stderr, "(bases / length), the largest depth, mismatches (X columns) and indels (I + D lengths). A deleted base is not\n");
+    std::fprintf(stderr, "covered. The bedgraph has name, start, end and depth per run, in the sequences' forward coordinates.\n\n");
+    return 1;
+}
+
+// six decimals of num / den from the integers, rounded half up: no floating point, the same digits everywhere
+std::string ratio6(uint64_t num, uint64_t den) {
+    const unsigned __int128 scaled = ((unsigned __int128)num * 2000000u + den) / ((unsigned __int128)den * 2);
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%llu.%06llu", (unsigned long long)(scaled / 1000000u), (unsigned long long)(scaled % 1000000u));
+    return buf;
+}
+
+}  // namespace
+
+int cover_main(int argc, char** argv) {
+    if (argc == 1) return spumoni_cover_usage();
+    ReadOptions o;
+    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
+    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6, min_depth = 1;
+    bool bedgraph = false;
+    parse_read_options(argc, argv, o, spumoni_cover_usage, true, "L:S:G:B:H:F:E:O:N:I:D:b",
+                       {{"min-length", required_argument, NULL, 'L'},
+                        {"max-dist", required_argument, NULL, 'S'},
+                        {"max-gap", required_argument, NULL, 'G'},
+                        {"gap-penalty", required_argument, NULL, 'B'},
+                        {"lookback", required_argument, NULL, 'H'},
+                        {"max-fill", required_argument, NULL, 'F'},
+                        {"max-extend", required_argument, NULL, 'E'},
+                        {"band", required_argument, NULL, 'O'},
+                        {"mismatch", required_argument, NULL, 'N'},
+                        {"indel", required_argument, NULL, 'I'},
+                        {"min-depth", required_argument, NULL, 'D'},
+                        {"bedgraph", no_argument, NULL, 'b'}},
+                       [&](int c, const char* arg) {
+                           if (c == 'b') {
+                               bedgraph = true;
+                           } else if (c == 'L') {
+                               o.have_threshold = true;
+                               o.threshold = std::strtoull(arg, nullptr, 10);
+                           } else {
+                               (c == 'S'   ? max_dist
+                                : c == 'G' ? max_gap
+                                : c == 'B' ? gap_penalty
+                                : c == 'H' ? lookback
+                                : c == 'F' ? max_fill
+                                : c == 'E' ? max_extend
+                                : c == 'O' ? band
+                                : c == 'N' ? mismatch
+                                : c == 'I' ? indel
+                                           : min_depth) = arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
+                           }
+                       });
+    require_ref_and_pattern(o);
+    if (o.pml_requested)
+        fatal_warning("-P cannot be used with `spumoni cover`: the anchors are read off matching statistics (-M is implied); "
+                      "PMLs have no pointers.");
+    if (o.use_promotions || o.use_dna_letters)
+        fatal_warning("-m / -a cannot be used with `spumoni cover`: digested coordinates cannot be turned back into bases. "
+                      "Map against an index built with -n -s.");
+    if (o.min_digest)
+        fatal_warning("`spumoni cover` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
+    o.ms = true;
+    validate_read_options(o);
+    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
+    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
+    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
+    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
+    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
+    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
+    if (max_extend < 1 || max_extend > 4096) fatal_warning("the largest extended end (-E) must be between 1 and 4096.");
+    if (band > 63) fatal_warning("the band (-O) must be between 0 and 63.");
+    if (mismatch > 65535) fatal_warning("the mismatch cost (-N) must be between 0 and 65535.");
+    if (indel > 65535) fatal_warning("the indel cost (-I) must be between 0 and 65535.");
+    if (min_depth > 4294967295ull) fatal_warning("the smallest depth (-D) must be between 0 and 4294967295.");
+    o.ref_file += ".fa";
+    const std::string table_path = o.ref_file + ".seqs";
+    if (!is_file(table_path))
+        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", table_path.c_str());
+    const SeqTable table = read_seq_table(table_path);
+    const std::vector<void*> entry =
+        device_entry_points("cover", {"spd_cover_add_batch", "spn_set_sequences", "spd_cover_reset", "spd_cover_summary",
+                                      "spd_cover_runs_begin", "spd_cover_runs_fetch"}, "the coverage kernels");
+    auto add_batch = reinterpret_cast<decltype(&spd_cover_add_batch)>(entry[0]);
+    auto set_sequences = reinterpret_cast<decltype(&spn_set_sequences)>(entry[1]);
+    auto reset = reinterpret_cast<decltype(&spd_cover_reset)>(entry[2]);
+    auto summary = reinterpret_cast<decltype(&spd_cover_summary)>(entry[3]);
+    auto runs_begin = reinterpret_cast<decltype(&spd_cover_runs_begin)>(entry[4]);
+    auto runs_fetch = reinterpret_cast<decltype(&spd_cover_runs_fetch)>(entry[5]);
+    ReadRun run;
+    open_read_run(o, 8u << 20, run);
+    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spd_cover_add_batch)
+    if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
+        fatal_error("%s: %s", table_path.c_str(), spx_last_error());
+    if (reset(run.ix) != SPX_OK) fatal_error("%s", spx_last_error());
+    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
+    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
+    const spa_params fill{(uint32_t)max_fill};
+    const spe_params ends{(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel};
+    std::fprintf(stderr, "[cover] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); a match is an anchor from length %llu on "
+                 "(max-dist %llu, max-gap %llu, gap penalty %llu, lookback %llu, max-fill %llu, max-extend %llu, band %llu, mismatch %llu, "
+                 "indel %llu)\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
+                 (unsigned long long)min_length, max_dist, max_gap, gap_penalty, lookback, max_fill, max_extend, band, mismatch, indel);
+
+    LinesFile none;  // (nothing is written per read)
+    none.keep_partial = false;
+    uint64_t num_reads = 0, num_mapped = 0;
+    std::vector<spn_mapping> maps;
+    scan_reads(
+        run, none,
+        [&](ReadBatch& b) {
+            maps.resize(b.take + 1);
+            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
+            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
+                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+                if (add_batch(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
+                              o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0) != SPX_OK)
+                    fatal_error("%s", spx_last_error());
+                // (without digestion a read's values are its characters)
+                for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
+            }
+        },
+        [&](const ReadBatch&, size_t i) {
+            num_reads++;
+            num_mapped += maps[i].seq != SPN_UNMAPPED;
+        });
+    // everything that can fail on the device comes before the first file
+    std::vector<spd_seq_cover> cover(table.names.size());
+    if (summary(run.ix, cover.data(), cover.size()) != SPX_OK) fatal_error("%s", spx_last_error());
+    std::vector<spd_run> runs;
+    if (bedgraph) {
+        uint64_t n = 0;
+        if (runs_begin(run.ix, (uint32_t)min_depth, &n) != SPX_OK) fatal_error("%s", spx_last_error());
+        runs.resize(n + 1);
+        if (runs_fetch(run.ix, runs.data()) != SPX_OK) fatal_error("%s", spx_last_error());
+        runs.resize(n);
+    }
+    uint64_t added = 0;
+    for (const spd_seq_cover& c : cover) added += c.reads;
+    const std::string bed_path = o.pattern_file + ".bedgraph";
+    if (bedgraph) {
+        LinesFile bed;
+        bed.open(bed_path, false);
+        for (const spd_run& r : runs)
+            std::fprintf(bed.f, "%s\t%llu\t%llu\t%u\n", table.names[r.seq].c_str(), (unsigned long long)r.start, (unsigned long long)r.end,
+                         r.depth);
+        bed.close();
+    }
+    LinesFile out;
+    out.open(o.pattern_file + ".cover", false);
+    for (size_t s = 0; s < cover.size(); ++s) {
+        const spd_seq_cover& c = cover[s];
+        const uint64_t len = table.lengths[s];
+        std::fprintf(out.f, "%s\t%llu\t%llu\t%llu\t%s\t%llu\t%s\t%u\t%llu\t%llu\n", table.names[s].c_str(), (unsigned long long)len,
+                     (unsigned long long)c.reads, (unsigned long long)c.covered, ratio6(c.covered, len).c_str(), (unsigned long long)c.bases,
+                     ratio6(c.bases, len).c_str(), c.max_depth, (unsigned long long)c.mismatches, (unsigned long long)c.indels);
+    }
+    if (std::fflush(out.f) != 0 || std::ferror(out.f)) {
+        if (bedgraph) ::unlink(bed_path.c_str());  // (a run that fails leaves no file: this one was complete already)
+        fatal_error("write failed (disk full?): %s", out.path.c_str());
+    }
+    out.close();
+    std::fprintf(stderr, "[cover] %llu reads, %llu mapped, %llu added to the coverage, %llu without a mapping (%.3f sec). results are saved in "
+                 "*.cover%s\n",
+                 (unsigned long long)num_reads, (unsigned long long)num_mapped, (unsigned long long)added,
+                 (unsigned long long)(num_reads - num_mapped),
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count(), bedgraph ? " and *.bedgraph" : "");
+    return 0;
+}

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 
 #include "index_files.hpp"
@@ -139,6 +140,43 @@ uint64_t null_db_threshold(const ReadOptions& o) {
     std::string err;
     (void)load_null_db(o.ref_file + (o.ms ? ".msnulldb" : ".pmlnulldb"), percentile, err);
     return max_value_threshold(percentile, !o.ms, o.use_promotions, o.use_dna_letters);
+}
+
+// name<TAB>length<TAB>text_start<TAB>strands per line (spumoni_amd/map.py: read_seq_table)
+SeqTable read_seq_table(const std::string& path) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) fatal_error("cannot read %s", path.c_str());
+    SeqTable t;
+    std::string line;
+    uint64_t start = 0, lineno = 0;
+    while (std::getline(in, line)) {
+        ++lineno;
+        if (line.empty()) continue;
+        std::vector<std::string> f;
+        for (size_t at = 0;;) {
+            const size_t tab = line.find('\t', at);
+            f.push_back(line.substr(at, tab == std::string::npos ? tab : tab - at));
+            if (tab == std::string::npos) break;
+            at = tab + 1;
+        }
+        bool ok = f.size() == 4 && !f[0].empty();
+        unsigned long long v[3] = {0, 0, 0};
+        for (int i = 0; ok && i < 3; ++i) {
+            const std::string& s = f[i + 1];
+            ok = !s.empty() && s.size() <= 19 && s.find_first_not_of("0123456789") == std::string::npos;
+            if (ok) v[i] = std::strtoull(s.c_str(), nullptr, 10);
+        }
+        if (!ok) fatal_error("%s: line %llu is not name<TAB>length<TAB>text_start<TAB>strands", path.c_str(), (unsigned long long)lineno);
+        if (v[2] < 1 || v[2] > 2 || (t.strands && v[2] != t.strands) || v[0] == 0 || v[1] != start)
+            fatal_error("%s: line %llu: strands, length or text_start do not fit the lines before it", path.c_str(),
+                        (unsigned long long)lineno);
+        t.strands = (uint32_t)v[2];
+        t.names.push_back(f[0]);
+        t.lengths.push_back(v[0]);
+        start += v[0] * v[2];
+    }
+    if (t.names.empty()) fatal_error("%s: no sequences", path.c_str());
+    return t;
 }
 
 namespace {

@@ -65,6 +65,14 @@ struct LinesFile {
     void close();
 };
 
+// <prefix>.fa.seqs, the table `spumoni build -s` writes (`map`, `cover`): ends the process on a malformed table
+struct SeqTable {
+    std::vector<std::string> names;
+    std::vector<uint64_t> lengths;
+    uint32_t strands = 0;
+};
+SeqTable read_seq_table(const std::string& path);
+
 struct ReadBatch {
     std::vector<ReadRec> recs;  // the first `take` are the batch
     size_t take = 0;

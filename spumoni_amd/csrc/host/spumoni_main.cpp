@@ -382,6 +382,7 @@ int align_main(int argc, char** argv);  // align_main.cpp
 int cigar_main(int argc, char** argv);  // cigar_main.cpp
 int extend_main(int argc, char** argv);  // extend_main.cpp
 int map_main(int argc, char** argv);  // map_main.cpp
+int cover_main(int argc, char** argv);  // cover_main.cpp
 
 static int spumoni_usage() {
     std::fprintf(stderr, "SPUMONI has different sub-commands to run which can used as follows:\n");
@@ -396,7 +397,8 @@ static int spumoni_usage() {
     std::fprintf(stderr, "\talign\taligns each read along its best chain from an MS index: edits and matches with every gap filled.\n");
     std::fprintf(stderr, "\tcigar\taligns each read as `align` does and reports the path of the alignment as a CIGAR.\n");
     std::fprintf(stderr, "\textend\treports the CIGAR of `cigar` taken to the read's ends: both ends extended in a band, the rest soft-clipped.\n");
-    std::fprintf(stderr, "\tmap\tmaps each read: the alignment of `extend` by sequence name, strand and position in the sequence, as PAF.\n\n");
+    std::fprintf(stderr, "\tmap\tmaps each read: the alignment of `extend` by sequence name, strand and position in the sequence, as PAF.\n");
+    std::fprintf(stderr, "\tcover\tmaps each read as `map` does and reports per sequence how much of it the reads cover and how deep.\n\n");
     return 1;
 }
 
@@ -415,6 +417,7 @@ int main(int argc, char** argv) {
         if (std::strcmp(argv[1], "cigar") == 0) return cigar_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "extend") == 0) return extend_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "map") == 0) return map_main(argc - 1, argv + 1);
+        if (std::strcmp(argv[1], "cover") == 0) return cover_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "run") == 0) {
             const int rc = run_main(argc - 1, argv + 1);
             if (std::getenv("SPX_FREE_TRACE")) std::fprintf(stderr, "[spumoni] main returns %d\n", rc);

@@ -184,6 +184,7 @@ void spx_index_free(spx_index* ix) {
     release_cigar(ix);
     release_extend(ix);
     release_map(ix);
+    release_cover(ix);
     if (ix->ev_dig) (void)hipEventDestroy(ix->ev_dig);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
@@ -558,6 +559,14 @@ int spx_set_option(spx_index* ix, const char* key, int64_t value) {
     }
     if (!strcmp(key, "digest_kernel")) {
         ix->force_digest_kernel = (int)value;
+        return SPX_OK;
+    }
+    if (!strcmp(key, "cover_switch")) {  // spx_cover.hip: a read of more entries than this takes a wavefront (measurement, tests)
+        if (value < 0 || value > 0x7fffffff) {
+            set_error("cover_switch must be between 0 and 2^31 - 1");
+            return SPX_E_ARG;
+        }
+        ix->cover_switch = (int)value;
         return SPX_OK;
     }
     if (!strcmp(key, "minimizer_charhash")) {

@@ -360,6 +360,20 @@ struct spx_index {
     uint64_t map_acc[8] = {};
     bool map_ready = false;
     uint64_t map_ready_n = 0, map_ready_reads = 0;
+    // coverage (spx_cover.hip): one Product per step -- add, finish, runs --, so that each keeps its counters and its
+    // events; the list of the reads that take a wavefront, the scans' space, the runs' tile counts and offsets (under
+    // mu); then the host forms' arrays -- diff, mism, depth, the per-sequence counts --, the summary, the runs and their
+    // count (under host_mu).  cover_G: the forward genome the arrays were sized for, 0 without a reset; cover_dropped:
+    // spn_set_sequences took them away; cover_mapped: mapped reads added since the reset; cover_dirty: depth is older
+    // than diff.  cover_acc: reads, mapped, added, skipped, intervals, atomics of the adds the stats speak of
+    enum { D_LONG, D_CUB, D_CUB2, D_TCNT, D_TOFFS, D_DIFF, D_MISM, D_DEPTH, D_COUNTS, D_OUT, D_RUNS, D_NRUNS, D_COUNT };
+    Scratch cover_scr[D_COUNT];
+    Product cover_add, cover_fin, cover_runs;  // (acc unused: cover_acc)
+    uint64_t cover_G = 0, cover_mapped = 0, cover_acc[6] = {}, cover_nruns = 0;
+    bool cover_dropped = false, cover_dirty = false, cover_runs_ready = false;
+    uint64_t cover_runs_ready_n = 0;
+    int cover_switch = 64;  // "cover_switch" option: a read of more entries than this takes a wavefront
+    float cover_step_ms[3] = {};
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -500,6 +514,12 @@ void release_extend(spx_index* ix);
 // spx_map.hip: the same for the mappings and the sequence table; and the table of `src` copied into a fresh clone
 void release_map(spx_index* ix);
 int clone_map(spx_index* src, spx_index* ix);
+// spx_cover.hip: the same for the coverage; and what spn_set_sequences does to it (the caller holds host_mu and mu): the
+// host forms' arrays were sized for the table that goes
+void release_cover(spx_index* ix);
+void cover_table_changed(spx_index* ix);
+// ... and a fresh clone of an index that has the arrays gets its own, empty
+int clone_cover(spx_index* src, spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on
