@@ -1037,6 +1037,104 @@ class Index:
         out["step_ms"] = list(s.step_ms)
         return out
 
+    # -- pileup and calls (include/spumoni_call.h) ------------------------------------------
+    def pileup_add_device(self, d_mappings, d_op_offsets, d_ops, d_reads, d_read_offsets, d_alt, d_other, d_ins, d_ddiff, in_entries=None,
+                          in_chars=None, stream=None) -> None:
+        """map_device's (d_out, d_out_op_offsets, d_out_ops) and the reads' bytes (d_reads uint8, d_read_offsets int64[reads + 1])
+        added to d_alt int32[4 * G], d_other int32[G], d_ins int32[G] and d_ddiff int32[G + 1] (call.py).  in_entries and
+        in_chars default to d_ops' and d_reads' sizes."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        nreads = d_op_offsets.numel() - 1
+        if in_entries is None:
+            in_entries = d_ops.numel()
+        if in_chars is None:
+            in_chars = d_reads.numel()
+        _check(_spl().spl_pileup_add_device(self._h, _t_ptr(d_mappings), _t_ptr(d_op_offsets), _t_ptr(d_ops), int(in_entries),
+                                            _t_ptr(d_reads), _t_ptr(d_read_offsets), int(in_chars), nreads, _t_ptr(d_alt), _t_ptr(d_other),
+                                            _t_ptr(d_ins), _t_ptr(d_ddiff), C.c_void_p(st.cuda_stream)))
+
+    def pileup_finish_device(self, d_ddiff, d_del=None, stream=None):
+        """d_del int32[G]: the running sum of d_ddiff, which stays as it is."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if d_del is None:
+            d_del = torch.empty(d_ddiff.numel() - 1, dtype=torch.int32, device=d_ddiff.device)
+        _check(_spl().spl_pileup_finish_device(self._h, _t_ptr(d_ddiff), _t_ptr(d_del), C.c_void_p(st.cuda_stream)))
+        return d_del
+
+    def calls_device(self, d_depth, d_mism, d_alt, d_other, d_ins, d_del, min_depth=2, min_alt=2, min_permille=500, call_capacity=0,
+                     d_calls=None, d_count=None, stream=None):
+        """(d_calls int64 (call_capacity, 6), a view of call.CALL_DTYPE; d_count int64[1]): the calls of the arrays."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if d_calls is None:
+            d_calls = torch.empty((max(int(call_capacity), 1), 6), dtype=torch.int64, device=d_depth.device)
+        if d_count is None:
+            d_count = torch.empty(1, dtype=torch.int64, device=d_depth.device)
+        _check(_spl().spl_calls_device(self._h, _t_ptr(d_depth), _t_ptr(d_mism), _t_ptr(d_alt), _t_ptr(d_other), _t_ptr(d_ins), _t_ptr(d_del),
+                                       int(min_depth), int(min_alt), int(min_permille), int(call_capacity), _t_ptr(d_calls), _t_ptr(d_count),
+                                       C.c_void_p(st.cuda_stream)))
+        return d_calls, d_count
+
+    def call_reset(self) -> None:
+        """cover_reset, and the handle's pileup arrays allocated for the sequence table in force, or zeroed."""
+        _check(_spl().spl_call_reset(self._h))
+
+    def call_add_host(self, seqs, offs, min_length, chain_params=None, params=None, extend_params=None, digest=None, want_docs=False):
+        """spl_call_add_batch: cover_add_host's arguments; the mappings are added to the handle's coverage and to its
+        pileup on the device and come back (map.MAPPING_DTYPE[reads])."""
+        from .align import AlignParams
+        from .chain import ChainParams
+        from .extend import ExtendParams
+        from .map import MAPPING_DTYPE
+
+        L = _spl()
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nreads = offs.size - 1
+        kind, k, w = digest if digest else (0, 0, 0)
+        out = np.zeros(max(nreads, 1), dtype=MAPPING_DTYPE)
+        cp = SpcParams(*(int(v) for v in (ChainParams() if chain_params is None else chain_params)))
+        ap = SpaParams(*(int(v) for v in (AlignParams() if params is None else params)))
+        ep = SpeParams(*(int(v) for v in (ExtendParams() if extend_params is None else extend_params)))
+        _check(L.spl_call_add_batch(self._h, kind, k, w, _np_ptr(seqs), _np_ptr(offs), nreads, int(min_length), 1 if want_docs else 0,
+                                    C.byref(cp), C.byref(ap), C.byref(ep), _np_ptr(out)))
+        return out[:nreads]
+
+    def calls(self, min_depth: int = 2, min_alt: int = 2, min_permille: int = 500) -> np.ndarray:
+        """spl_calls_begin + _fetch: call.CALL_DTYPE[] in (sequence, position) order."""
+        from .call import CALL_DTYPE
+
+        L = _spl()
+        n = C.c_uint64(0)
+        _check(L.spl_calls_begin(self._h, int(min_depth), int(min_alt), int(min_permille), C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=CALL_DTYPE)
+        _check(L.spl_calls_fetch(self._h, _np_ptr(out)))
+        return out[:n.value]
+
+    def pileup_counts(self, first: int, count: int):
+        """(alt uint32 (count, 4), other, ins, del uint32[count]) of the positions [first, first + count) of the forward genome."""
+        n = max(int(count), 1)
+        alt, other, ins, dele = (np.zeros(4 * n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32),
+                                 np.zeros(n, dtype=np.uint32))
+        _check(_spl().spl_pileup_counts(self._h, int(first), int(count), _np_ptr(alt), _np_ptr(other), _np_ptr(ins), _np_ptr(dele)))
+        return alt[:4 * int(count)].reshape(-1, 4), other[:int(count)], ins[:int(count)], dele[:int(count)]
+
+    def call_stats(self) -> dict:
+        """Of the most recent pileup and calls steps: the reads, the mapped, added and skipped ones, the 'X' columns, those
+        of a byte outside ACGT, the 'I' and 'D' entries and the atomic adds of the adds (since call_reset for
+        call_add_host, of the last call for pileup_add_device), the calls of the last calls step, the error and overflow
+        flags and the time of the last add, finish and calls step."""
+        s = SplCallStats()
+        _check(_spl().spl_last_call_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SplCallStats._fields_ if f[0] != "reserved"}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
     def last_chunk_stats(self) -> dict:
         """Chunked walk of the last query: chunk size (0 = it ran the plain walk), characters walked a second
         time to join the chunks, reads that fell back to the plain walk."""
@@ -1357,6 +1455,41 @@ def _spd() -> C.CDLL:
         L.spd_cover_depth.argtypes = [vp, u64, u64, vp, vp]
         L.spd_last_cover_stats.argtypes = [vp, C.POINTER(SpdCoverStats)]
         _SPD_READY = True
+    return L
+
+
+# ---- the pileup and the calls (include/spumoni_call.h) ---------------------------------------------------------------
+CALL_EXPORTS = ["spl_pileup_add_device", "spl_pileup_finish_device", "spl_calls_device", "spl_call_reset", "spl_call_add_batch",
+                "spl_calls_begin", "spl_calls_fetch", "spl_pileup_counts", "spl_last_call_stats"]
+_SPL_READY = False
+
+
+class SplCallStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("mapped", C.c_uint64), ("added", C.c_uint64), ("skipped", C.c_uint64),
+                ("x_columns", C.c_uint64), ("other_columns", C.c_uint64), ("insertions", C.c_uint64), ("deletions", C.c_uint64),
+                ("atomics", C.c_uint64), ("calls", C.c_uint64), ("error", C.c_uint32), ("overflow", C.c_uint32),
+                ("step_ms", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+def _spl() -> C.CDLL:
+    """The library with the spl_* argtypes set (on first use)."""
+    global _SPL_READY
+    L = _spd()
+    if not hasattr(L, "spl_call_add_batch"):
+        raise SpxError(f"{LIB_PATH} has no pileup kernels (spl_call_add_batch): there is no CPU fallback")
+    if not _SPL_READY:
+        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+        L.spl_pileup_add_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, u64, vp, vp, vp, vp, vp]
+        L.spl_pileup_finish_device.argtypes = [vp, vp, vp, vp]
+        L.spl_calls_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp]
+        L.spl_call_reset.argtypes = [vp]
+        L.spl_call_add_batch.argtypes = [vp, i32, u32, u32, vp, vp, u64, u64, i32, C.POINTER(SpcParams), C.POINTER(SpaParams),
+                                         C.POINTER(SpeParams), vp]
+        L.spl_calls_begin.argtypes = [vp, u32, u32, u32, C.POINTER(u64)]
+        L.spl_calls_fetch.argtypes = [vp, vp]
+        L.spl_pileup_counts.argtypes = [vp, u64, u64, vp, vp, vp, vp]
+        L.spl_last_call_stats.argtypes = [vp, C.POINTER(SplCallStats)]
+        _SPL_READY = True
     return L
 
 

@@ -383,6 +383,7 @@ int cigar_main(int argc, char** argv);  // cigar_main.cpp
 int extend_main(int argc, char** argv);  // extend_main.cpp
 int map_main(int argc, char** argv);  // map_main.cpp
 int cover_main(int argc, char** argv);  // cover_main.cpp
+int call_main(int argc, char** argv);  // call_main.cpp
 
 static int spumoni_usage() {
     std::fprintf(stderr, "SPUMONI has different sub-commands to run which can used as follows:\n");
@@ -398,7 +399,8 @@ static int spumoni_usage() {
     std::fprintf(stderr, "\tcigar\taligns each read as `align` does and reports the path of the alignment as a CIGAR.\n");
     std::fprintf(stderr, "\textend\treports the CIGAR of `cigar` taken to the read's ends: both ends extended in a band, the rest soft-clipped.\n");
     std::fprintf(stderr, "\tmap\tmaps each read: the alignment of `extend` by sequence name, strand and position in the sequence, as PAF.\n");
-    std::fprintf(stderr, "\tcover\tmaps each read as `map` does and reports per sequence how much of it the reads cover and how deep.\n\n");
+    std::fprintf(stderr, "\tcover\tmaps each read as `map` does and reports per sequence how much of it the reads cover and how deep.\n");
+    std::fprintf(stderr, "\tcall\tmaps each read as `map` does and reports where the reads support a letter other than the reference's, as VCF.\n\n");
     return 1;
 }
 
@@ -418,6 +420,7 @@ int main(int argc, char** argv) {
         if (std::strcmp(argv[1], "extend") == 0) return extend_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "map") == 0) return map_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "cover") == 0) return cover_main(argc - 1, argv + 1);
+        if (std::strcmp(argv[1], "call") == 0) return call_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "run") == 0) {
             const int rc = run_main(argc - 1, argv + 1);
             if (std::getenv("SPX_FREE_TRACE")) std::fprintf(stderr, "[spumoni] main returns %d\n", rc);

@@ -185,6 +185,7 @@ void spx_index_free(spx_index* ix) {
     release_extend(ix);
     release_map(ix);
     release_cover(ix);
+    release_call(ix);
     if (ix->ev_dig) (void)hipEventDestroy(ix->ev_dig);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
@@ -567,6 +568,14 @@ int spx_set_option(spx_index* ix, const char* key, int64_t value) {
             return SPX_E_ARG;
         }
         ix->cover_switch = (int)value;
+        return SPX_OK;
+    }
+    if (!strcmp(key, "call_switch")) {  // spx_call.hip: the same for the pileup's add
+        if (value < 0 || value > 0x7fffffff) {
+            set_error("call_switch must be between 0 and 2^31 - 1");
+            return SPX_E_ARG;
+        }
+        ix->call_switch = (int)value;
         return SPX_OK;
     }
     if (!strcmp(key, "minimizer_charhash")) {

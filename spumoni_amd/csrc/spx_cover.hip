@@ -740,6 +740,70 @@ void cover_table_changed(spx_index* ix) {
     ix->cover_dropped = true;
 }
 
+// What spd_cover_add_batch does behind its first check, for it and for spl_call_add_batch (spx_call.hip): `who` names the
+// caller in the messages; `also` (may be empty) is called under host_mu with the coverage's add enqueued and enqueues its
+// own work on the same records and entries, in front of the one wait.
+int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
+                         uint64_t nreads, uint64_t min_length, int want_docs, const spc_params* chain_params, const spa_params* align_params,
+                         const spe_params* extend_params, spn_mapping* out_mappings, const std::function<int(const CoverBatch&)>& also) {
+    int rc;
+    {
+        std::lock_guard<std::mutex> hg(ix->host_mu);
+        if ((rc = need_arrays(ix, who)) != SPX_OK) return rc;
+    }
+    // the pipeline up to the mappings is spn_map_begin itself: its checks, its waits, its results on the device
+    std::vector<spn_mapping> own;
+    if (!out_mappings && nreads) {
+        own.resize(nreads);
+        out_mappings = own.data();
+    }
+    uint64_t n_in = 0;
+    if ((rc = spn_map_begin(ix, digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, chain_params, align_params, extend_params,
+                            out_mappings, nullptr, &n_in)) != SPX_OK)
+        return rc;
+    std::lock_guard<std::mutex> hg(ix->host_mu);
+    SPX_HIP(hipSetDevice(ix->device));
+    // (another host thread on this handle between the two locks would have taken the entries, or the arrays)
+    if (!ix->map_ready || ix->map_ready_reads != nreads || ix->map_ready_n != n_in) {
+        set_error("%s: another call on this index took the mappings: calls on one handle must not overlap", who);
+        return SPX_E_ARG;
+    }
+    ix->map_ready = false;  // (the entries are this call's: nothing waits for spn_map_fetch)
+    if ((rc = need_arrays(ix, who)) != SPX_OK) return rc;
+    if (nreads == 0) return SPX_OK;
+    uint64_t mapped = 0;
+    for (uint64_t q = 0; q < nreads; ++q) mapped += out_mappings[q].seq != SPN_UNMAPPED;
+    if (mapped >= (1ull << 32) - ix->cover_mapped) {
+        set_error("%s: %llu mapped reads were added since spd_cover_reset and this batch has %llu: 2^32 or more could "
+                  "wrap a depth; nothing was added",
+                  who, (unsigned long long)ix->cover_mapped, (unsigned long long)mapped);
+        return SPX_E_ARG;
+    }
+    hipStream_t st = nullptr;
+    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
+    AddArgs a{};
+    const spn_mapping* d_maps = (const spn_mapping*)ix->map_scr[spx_index::N_OUT].p;
+    a.map = (const uint4*)d_maps;
+    a.ioffs = (const uint64_t*)ix->map_scr[spx_index::N_OOFFS].p;
+    a.iops = (const uint32_t*)ix->map_scr[spx_index::N_OPS].p;
+    a.in_entries = n_in;
+    a.nreads = nreads;
+    a.diff = (uint32_t*)ix->cover_scr[spx_index::D_DIFF].p;
+    a.mism = (uint32_t*)ix->cover_scr[spx_index::D_MISM].p;
+    a.counts = (unsigned long long*)ix->cover_scr[spx_index::D_COUNTS].p;
+    ix->cover_dirty = true;
+    ix->cover_runs_ready = false;
+    if ((rc = add_enqueue(ix, a, st)) != SPX_OK) return rc;
+    if (also && (rc = also(CoverBatch{d_maps, a.ioffs, a.iops, n_in, nreads, st})) != SPX_OK) return rc;
+    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
+    if ((rc = step_collect(ix, ix->cover_add, ADD_WORDS, 0)) != SPX_OK) return rc;
+    ix->cover_mapped += mapped;
+    return add_error_code(ix);
+}
+
+int cover_need_arrays(spx_index* ix, const char* who) { return need_arrays(ix, who); }
+int cover_finish_host(spx_index* ix) { return finish_host(ix); }
+
 }  // namespace spx
 
 using namespace spx;
@@ -859,56 +923,8 @@ int spd_cover_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, 
                         const spe_params* extend_params, spn_mapping* out_mappings) {
     int rc;
     if ((rc = need_table(ix, "spd_cover_add_batch")) != SPX_OK) return rc;
-    {
-        std::lock_guard<std::mutex> hg(ix->host_mu);
-        if ((rc = need_arrays(ix, "spd_cover_add_batch")) != SPX_OK) return rc;
-    }
-    // the pipeline up to the mappings is spn_map_begin itself: its checks, its waits, its results on the device
-    std::vector<spn_mapping> own;
-    if (!out_mappings && nreads) {
-        own.resize(nreads);
-        out_mappings = own.data();
-    }
-    uint64_t n_in = 0;
-    if ((rc = spn_map_begin(ix, digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, chain_params, align_params, extend_params,
-                            out_mappings, nullptr, &n_in)) != SPX_OK)
-        return rc;
-    std::lock_guard<std::mutex> hg(ix->host_mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    // (another host thread on this handle between the two locks would have taken the entries, or the arrays)
-    if (!ix->map_ready || ix->map_ready_reads != nreads || ix->map_ready_n != n_in) {
-        set_error("spd_cover_add_batch: another call on this index took the mappings: calls on one handle must not overlap");
-        return SPX_E_ARG;
-    }
-    ix->map_ready = false;  // (the entries are this call's: nothing waits for spn_map_fetch)
-    if ((rc = need_arrays(ix, "spd_cover_add_batch")) != SPX_OK) return rc;
-    if (nreads == 0) return SPX_OK;
-    uint64_t mapped = 0;
-    for (uint64_t q = 0; q < nreads; ++q) mapped += out_mappings[q].seq != SPN_UNMAPPED;
-    if (mapped >= (1ull << 32) - ix->cover_mapped) {
-        set_error("spd_cover_add_batch: %llu mapped reads were added since spd_cover_reset and this batch has %llu: 2^32 or more could "
-                  "wrap a depth; nothing was added",
-                  (unsigned long long)ix->cover_mapped, (unsigned long long)mapped);
-        return SPX_E_ARG;
-    }
-    hipStream_t st = nullptr;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    AddArgs a{};
-    a.map = (const uint4*)ix->map_scr[spx_index::N_OUT].p;
-    a.ioffs = (const uint64_t*)ix->map_scr[spx_index::N_OOFFS].p;
-    a.iops = (const uint32_t*)ix->map_scr[spx_index::N_OPS].p;
-    a.in_entries = n_in;
-    a.nreads = nreads;
-    a.diff = (uint32_t*)ix->cover_scr[spx_index::D_DIFF].p;
-    a.mism = (uint32_t*)ix->cover_scr[spx_index::D_MISM].p;
-    a.counts = (unsigned long long*)ix->cover_scr[spx_index::D_COUNTS].p;
-    ix->cover_dirty = true;
-    ix->cover_runs_ready = false;
-    if ((rc = add_enqueue(ix, a, st)) != SPX_OK) return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->cover_add, ADD_WORDS, 0)) != SPX_OK) return rc;
-    ix->cover_mapped += mapped;
-    return add_error_code(ix);
+    return cover_add_batch_with(ix, "spd_cover_add_batch", digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, chain_params,
+                                align_params, extend_params, out_mappings, nullptr);
 }
 
 int spd_cover_summary(spx_index* ix, spd_seq_cover* out, uint64_t n_seqs) {

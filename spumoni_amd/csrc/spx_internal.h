@@ -163,6 +163,9 @@ struct BatchArgs {
 }  // namespace spx
 
 struct spc_params;  // include/spumoni_chain.h
+struct spa_params;  // include/spumoni_align.h
+struct spe_params;  // include/spumoni_extend.h
+struct spn_mapping;  // include/spumoni_map.h
 
 namespace spx {
 // The device arrays of an index once more than one handle uses them: spx_index_clone onto the SAME device hands out a
@@ -374,6 +377,23 @@ struct spx_index {
     uint64_t cover_runs_ready_n = 0;
     int cover_switch = 64;  // "cover_switch" option: a read of more entries than this takes a wavefront
     float cover_step_ms[3] = {};
+    // pileup and calls (spx_call.hip): one Product per step -- add, finish, calls -- as the coverage has; the list of the
+    // reads that take a wavefront, the scans' space, the calls' tile counts and offsets (under mu); then the host forms'
+    // arrays -- alt, other, ins, ddiff, del --, the batch's reads and their offsets, the calls and their count (under
+    // host_mu).  call_G, call_dropped, call_dirty: as the coverage's, for del and ddiff.  call_acc: reads, mapped, added,
+    // skipped, X columns, other columns, 'I' entries, 'D' entries of the adds the stats speak of.  The reads are copied
+    // on a stream of the product's own, so that the copy overlaps spn_map_begin
+    enum { PL_LONG, PL_CUB, PL_CUB2, PL_TCNT, PL_TOFFS, PL_ALT, PL_OTHER, PL_INS, PL_DDIFF, PL_DEL, PL_READS, PL_ROFFS, PL_CALLS,
+           PL_NCALLS, PL_COUNT };
+    Scratch call_scr[PL_COUNT];
+    Product call_add, call_fin, call_calls;  // (acc unused: call_acc)
+    uint64_t call_G = 0, call_acc[8] = {}, call_ncalls = 0;
+    bool call_dropped = false, call_dirty = false, call_ready = false;
+    uint64_t call_ready_n = 0;
+    int call_switch = 64;  // "call_switch" option: a read of more entries than this takes a wavefront
+    float call_step_ms[3] = {};
+    hipStream_t call_copy_s = nullptr;
+    hipEvent_t call_copy_ev = nullptr;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -520,6 +540,26 @@ void release_cover(spx_index* ix);
 void cover_table_changed(spx_index* ix);
 // ... and a fresh clone of an index that has the arrays gets its own, empty
 int clone_cover(spx_index* src, spx_index* ix);
+// ... and what spd_cover_add_batch does behind its first check, for it and for spl_call_add_batch: `also` (may be empty)
+// enqueues the caller's own work on the records and entries of the batch, behind the coverage's add and in front of the
+// one wait; the host forms' arrays checked (the caller holds host_mu) and depth brought up to date
+struct CoverBatch {
+    const spn_mapping* d_mappings;
+    const uint64_t* d_op_offsets;
+    const uint32_t* d_ops;
+    uint64_t in_entries, nreads;
+    hipStream_t stream;
+};
+int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
+                         uint64_t nreads, uint64_t min_length, int want_docs, const struct ::spc_params* chain_params,
+                         const struct ::spa_params* align_params, const struct ::spe_params* extend_params, spn_mapping* out_mappings,
+                         const std::function<int(const CoverBatch&)>& also);
+int cover_need_arrays(spx_index* ix, const char* who);
+int cover_finish_host(spx_index* ix);
+// spx_call.hip: the same three for the pileup and the calls
+void release_call(spx_index* ix);
+void call_table_changed(spx_index* ix);
+int clone_call(spx_index* src, spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on

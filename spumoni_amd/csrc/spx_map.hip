@@ -403,8 +403,9 @@ void release_map(spx_index* ix) {
 
 int clone_map(spx_index* src, spx_index* ix) {
     if (!src->map_P) return SPX_OK;
-    const int rc = spn_set_sequences(ix, src->map_seq_lengths.data(), src->map_seq_lengths.size(), src->map_strands);
-    return rc != SPX_OK ? rc : clone_cover(src, ix);
+    int rc = spn_set_sequences(ix, src->map_seq_lengths.data(), src->map_seq_lengths.size(), src->map_strands);
+    if (rc != SPX_OK || (rc = clone_cover(src, ix)) != SPX_OK) return rc;
+    return clone_call(src, ix);
 }
 
 }  // namespace spx
@@ -469,6 +470,7 @@ int spn_set_sequences(spx_index* ix, const uint64_t* seq_lengths, uint64_t n_seq
     ix->map_seq_lengths.assign(seq_lengths, seq_lengths + n_seqs);
     ix->map_ready = false;
     cover_table_changed(ix);
+    call_table_changed(ix);
     return SPX_OK;
 }
 
