@@ -49,40 +49,14 @@ int spumoni_call_usage() {
 int call_main(int argc, char** argv) {
     if (argc == 1) return spumoni_call_usage();
     ReadOptions o;
-    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
-    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6, min_depth = 2, min_alt = 2, min_permille = 500;
-    parse_read_options(argc, argv, o, spumoni_call_usage, true, "L:S:G:B:H:F:E:O:N:I:D:A:Q:",
-                       {{"min-length", required_argument, NULL, 'L'},
-                        {"max-dist", required_argument, NULL, 'S'},
-                        {"max-gap", required_argument, NULL, 'G'},
-                        {"gap-penalty", required_argument, NULL, 'B'},
-                        {"lookback", required_argument, NULL, 'H'},
-                        {"max-fill", required_argument, NULL, 'F'},
-                        {"max-extend", required_argument, NULL, 'E'},
-                        {"band", required_argument, NULL, 'O'},
-                        {"mismatch", required_argument, NULL, 'N'},
-                        {"indel", required_argument, NULL, 'I'},
-                        {"min-depth", required_argument, NULL, 'D'},
-                        {"min-alt", required_argument, NULL, 'A'},
-                        {"min-permille", required_argument, NULL, 'Q'}},
+    MapOptions m(MapOptions::EXTEND);
+    unsigned long long min_depth = 2, min_alt = 2, min_permille = 500;
+    parse_read_options(argc, argv, o, spumoni_call_usage, true, m.shorts("D:A:Q:").c_str(),
+                       m.longs({{"min-depth", required_argument, NULL, 'D'},
+                                {"min-alt", required_argument, NULL, 'A'},
+                                {"min-permille", required_argument, NULL, 'Q'}}),
                        [&](int c, const char* arg) {
-                           if (c == 'L') {
-                               o.have_threshold = true;
-                               o.threshold = std::strtoull(arg, nullptr, 10);
-                           } else {
-                               (c == 'S'   ? max_dist
-                                : c == 'G' ? max_gap
-                                : c == 'B' ? gap_penalty
-                                : c == 'H' ? lookback
-                                : c == 'F' ? max_fill
-                                : c == 'E' ? max_extend
-                                : c == 'O' ? band
-                                : c == 'N' ? mismatch
-                                : c == 'I' ? indel
-                                : c == 'D' ? min_depth
-                                : c == 'A' ? min_alt
-                                           : min_permille) = arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
-                           }
+                           if (!m.set(o, c, arg)) (c == 'D' ? min_depth : c == 'A' ? min_alt : min_permille) = count_argument(arg);
                        });
     require_ref_and_pattern(o);
     if (o.pml_requested)
@@ -95,16 +69,7 @@ int call_main(int argc, char** argv) {
         fatal_warning("`spumoni call` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
     o.ms = true;
     validate_read_options(o);
-    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
-    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
-    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
-    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
-    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
-    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
-    if (max_extend < 1 || max_extend > 4096) fatal_warning("the largest extended end (-E) must be between 1 and 4096.");
-    if (band > 63) fatal_warning("the band (-O) must be between 0 and 63.");
-    if (mismatch > 65535) fatal_warning("the mismatch cost (-N) must be between 0 and 65535.");
-    if (indel > 65535) fatal_warning("the indel cost (-I) must be between 0 and 65535.");
+    m.validate(o);
     if (min_depth < 1 || min_depth > 4294967295ull) fatal_warning("the smallest depth (-D) must be between 1 and 4294967295.");
     if (min_alt < 1 || min_alt > 4294967295ull) fatal_warning("the fewest reads with the called letter (-A) must be between 1 and 4294967295.");
     if (min_permille > 1000) fatal_warning("the smallest share (-Q) must be between 0 and 1000 thousandths.");
@@ -128,16 +93,14 @@ int call_main(int argc, char** argv) {
     if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
         fatal_error("%s: %s", table_path.c_str(), spx_last_error());
     if (reset(run.ix) != SPX_OK) fatal_error("%s", spx_last_error());
-    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
-    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
-    const spa_params fill{(uint32_t)max_fill};
-    const spe_params ends{(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel};
-    std::fprintf(stderr, "[call] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); a match is an anchor from length %llu on "
-                 "(max-dist %llu, max-gap %llu, gap penalty %llu, lookback %llu, max-fill %llu, max-extend %llu, band %llu, mismatch %llu, "
-                 "indel %llu); a call needs depth %llu, %llu reads and %llu thousandths of the depth\n",
+    const uint64_t min_length = m.min_length(o);
+    const spc_params params = m.chain();
+    const spa_params fill = m.fill();
+    const spe_params ends = m.ends();
+    std::fprintf(stderr, "[call] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); %s; a call needs depth %llu, %llu reads and "
+                 "%llu thousandths of the depth\n",
                  (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
-                 (unsigned long long)min_length, max_dist, max_gap, gap_penalty, lookback, max_fill, max_extend, band, mismatch, indel,
-                 min_depth, min_alt, min_permille);
+                 m.describe(min_length).c_str(), min_depth, min_alt, min_permille);
 
     LinesFile none;  // (nothing is written per read)
     none.keep_partial = false;
@@ -147,15 +110,13 @@ int call_main(int argc, char** argv) {
         run, none,
         [&](ReadBatch& b) {
             maps.resize(b.take + 1);
-            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
-            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
-                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+            for_each_piece(b, [&](size_t q0, size_t q1) {
                 if (add_batch(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
                               o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0) != SPX_OK)
                     fatal_error("%s", spx_last_error());
                 // (without digestion a read's values are its characters)
                 for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
-            }
+            });
         },
         [&](const ReadBatch&, size_t i) {
             num_reads++;

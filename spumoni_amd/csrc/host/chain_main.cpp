@@ -48,45 +48,26 @@ int spumoni_chain_usage() {
 int chain_main(int argc, char** argv) {
     if (argc == 1) return spumoni_chain_usage();
     ReadOptions o;
-    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64;
-    parse_read_options(argc, argv, o, spumoni_chain_usage, true, "L:S:G:B:H:",
-                       {{"min-length", required_argument, NULL, 'L'},
-                        {"max-dist", required_argument, NULL, 'S'},
-                        {"max-gap", required_argument, NULL, 'G'},
-                        {"gap-penalty", required_argument, NULL, 'B'},
-                        {"lookback", required_argument, NULL, 'H'}},
-                       [&](int c, const char* arg) {
-                           if (c == 'L') {
-                               o.have_threshold = true;
-                               o.threshold = std::strtoull(arg, nullptr, 10);
-                           } else {
-                               (c == 'S' ? max_dist : c == 'G' ? max_gap : c == 'B' ? gap_penalty : lookback) =
-                                   arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
-                           }
-                       });
+    MapOptions m(MapOptions::CHAIN);
+    parse_read_options(argc, argv, o, spumoni_chain_usage, true, m.shorts().c_str(), m.longs(),
+                       [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
     if (o.pml_requested)
         fatal_warning("-P cannot be used with `spumoni chain`: the anchors are read off matching statistics (-M is implied); "
                       "PMLs have no pointers.");
     o.ms = true;
     validate_read_options(o);
-    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
-    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
-    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
-    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
-    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
+    m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";
     auto chain_batch = reinterpret_cast<decltype(&spc_chain_batch)>(
         device_entry_points("chain", {"spc_chain_batch"}, "the chain kernel")[0]);
     ReadRun run;
     open_read_run(o, 8u << 20, run);
     run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spc_chain_batch)
-    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
-    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
-    std::fprintf(stderr, "[chain] index loaded (n = %llu, r = %llu); a match is an anchor from length %llu on (max-dist %llu, max-gap %llu, "
-                 "gap penalty %llu, lookback %llu)\n",
-                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)min_length, max_dist, max_gap,
-                 gap_penalty, lookback);
+    const uint64_t min_length = m.min_length(o);
+    const spc_params params = m.chain();
+    std::fprintf(stderr, "[chain] index loaded (n = %llu, r = %llu); %s\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, m.describe(min_length).c_str());
 
     LinesFile out;
     out.open(o.pattern_file + ".chains", false);
@@ -96,13 +77,11 @@ int chain_main(int argc, char** argv) {
         run, out,
         [&](ReadBatch& b) {
             chains.resize(b.take + 1);
-            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
-            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
-                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+            for_each_piece(b, [&](size_t q0, size_t q1) {
                 if (chain_batch(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
                                 min_length, o.use_doc ? 1 : 0, &params, chains.data() + q0, b.values.data() + q0) != SPX_OK)
                     fatal_error("%s", spx_last_error());
-            }
+            });
         },
         [&](const ReadBatch& b, size_t i) {
             const spc_chain& c = chains[i];

@@ -53,35 +53,16 @@ int spumoni_cigar_usage() {
 int cigar_main(int argc, char** argv) {
     if (argc == 1) return spumoni_cigar_usage();
     ReadOptions o;
-    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
-    parse_read_options(argc, argv, o, spumoni_cigar_usage, true, "L:S:G:B:H:F:",
-                       {{"min-length", required_argument, NULL, 'L'},
-                        {"max-dist", required_argument, NULL, 'S'},
-                        {"max-gap", required_argument, NULL, 'G'},
-                        {"gap-penalty", required_argument, NULL, 'B'},
-                        {"lookback", required_argument, NULL, 'H'},
-                        {"max-fill", required_argument, NULL, 'F'}},
-                       [&](int c, const char* arg) {
-                           if (c == 'L') {
-                               o.have_threshold = true;
-                               o.threshold = std::strtoull(arg, nullptr, 10);
-                           } else {
-                               (c == 'S' ? max_dist : c == 'G' ? max_gap : c == 'B' ? gap_penalty : c == 'H' ? lookback : max_fill) =
-                                   arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
-                           }
-                       });
+    MapOptions m(MapOptions::FILL);
+    parse_read_options(argc, argv, o, spumoni_cigar_usage, true, m.shorts().c_str(), m.longs(),
+                       [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
     if (o.pml_requested)
         fatal_warning("-P cannot be used with `spumoni cigar`: the anchors are read off matching statistics (-M is implied); "
                       "PMLs have no pointers.");
     o.ms = true;
     validate_read_options(o);
-    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
-    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
-    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
-    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
-    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
-    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
+    m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";
     const std::vector<void*> entry = device_entry_points("cigar", {"spg_cigar_begin", "spg_cigar_fetch"}, "the cigar kernels");
     auto cigar_begin = reinterpret_cast<decltype(&spg_cigar_begin)>(entry[0]);
@@ -89,13 +70,11 @@ int cigar_main(int argc, char** argv) {
     ReadRun run;
     open_read_run(o, 8u << 20, run);
     run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spg_cigar_begin)
-    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
-    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
-    const spa_params fill{(uint32_t)max_fill};
-    std::fprintf(stderr, "[cigar] index loaded (n = %llu, r = %llu); a match is an anchor from length %llu on (max-dist %llu, max-gap %llu, "
-                 "gap penalty %llu, lookback %llu, max-fill %llu)\n",
-                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)min_length, max_dist, max_gap,
-                 gap_penalty, lookback, max_fill);
+    const uint64_t min_length = m.min_length(o);
+    const spc_params params = m.chain();
+    const spa_params fill = m.fill();
+    std::fprintf(stderr, "[cigar] index loaded (n = %llu, r = %llu); %s\n",
+                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, m.describe(min_length).c_str());
 
     LinesFile out;
     out.open(o.pattern_file + ".cigars", false);
@@ -110,9 +89,7 @@ int cigar_main(int argc, char** argv) {
             recs.resize(b.take + 1);
             op_offs.assign(b.take + 1, 0);
             ops.clear();
-            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
-            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
-                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+            for_each_piece(b, [&](size_t q0, size_t q1) {
                 uint64_t n = 0;
                 if (cigar_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
                                 min_length, o.use_doc ? 1 : 0, &params, &fill, recs.data() + q0, nullptr, b.values.data() + q0,
@@ -124,7 +101,7 @@ int cigar_main(int argc, char** argv) {
                 if (cigar_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
                 ops.resize(at + n);
                 for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
-            }
+            });
         },
         [&](const ReadBatch& b, size_t i) {
             const spa_alignment& c = recs[i];

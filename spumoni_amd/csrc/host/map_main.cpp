@@ -60,35 +60,9 @@ int spumoni_map_usage() {
 int map_main(int argc, char** argv) {
     if (argc == 1) return spumoni_map_usage();
     ReadOptions o;
-    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
-    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6;
-    parse_read_options(argc, argv, o, spumoni_map_usage, true, "L:S:G:B:H:F:E:O:N:I:",
-                       {{"min-length", required_argument, NULL, 'L'},
-                        {"max-dist", required_argument, NULL, 'S'},
-                        {"max-gap", required_argument, NULL, 'G'},
-                        {"gap-penalty", required_argument, NULL, 'B'},
-                        {"lookback", required_argument, NULL, 'H'},
-                        {"max-fill", required_argument, NULL, 'F'},
-                        {"max-extend", required_argument, NULL, 'E'},
-                        {"band", required_argument, NULL, 'O'},
-                        {"mismatch", required_argument, NULL, 'N'},
-                        {"indel", required_argument, NULL, 'I'}},
-                       [&](int c, const char* arg) {
-                           if (c == 'L') {
-                               o.have_threshold = true;
-                               o.threshold = std::strtoull(arg, nullptr, 10);
-                           } else {
-                               (c == 'S'   ? max_dist
-                                : c == 'G' ? max_gap
-                                : c == 'B' ? gap_penalty
-                                : c == 'H' ? lookback
-                                : c == 'F' ? max_fill
-                                : c == 'E' ? max_extend
-                                : c == 'O' ? band
-                                : c == 'N' ? mismatch
-                                           : indel) = arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10);
-                           }
-                       });
+    MapOptions m(MapOptions::EXTEND);
+    parse_read_options(argc, argv, o, spumoni_map_usage, true, m.shorts().c_str(), m.longs(),
+                       [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
     if (o.pml_requested)
         fatal_warning("-P cannot be used with `spumoni map`: the anchors are read off matching statistics (-M is implied); "
@@ -100,16 +74,7 @@ int map_main(int argc, char** argv) {
         fatal_warning("`spumoni map` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
     o.ms = true;
     validate_read_options(o);
-    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
-    if (max_dist < 1 || max_dist > 2147483647ull) fatal_warning("the largest distance (-S) must be between 1 and 2147483647.");
-    if (max_gap > 2147483647ull) fatal_warning("the largest gap (-G) must be between 0 and 2147483647.");
-    if (gap_penalty > 65535) fatal_warning("the gap penalty (-B) must be between 0 and 65535.");
-    if (lookback < 1 || lookback > 64) fatal_warning("the lookback (-H) must be between 1 and 64.");
-    if (max_fill < 1 || max_fill > 4096) fatal_warning("the largest filled gap (-F) must be between 1 and 4096.");
-    if (max_extend < 1 || max_extend > 4096) fatal_warning("the largest extended end (-E) must be between 1 and 4096.");
-    if (band > 63) fatal_warning("the band (-O) must be between 0 and 63.");
-    if (mismatch > 65535) fatal_warning("the mismatch cost (-N) must be between 0 and 65535.");
-    if (indel > 65535) fatal_warning("the indel cost (-I) must be between 0 and 65535.");
+    m.validate(o);
     o.ref_file += ".fa";
     const std::string table_path = o.ref_file + ".seqs";
     if (!is_file(table_path))
@@ -125,15 +90,13 @@ int map_main(int argc, char** argv) {
     run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spn_map_begin)
     if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
         fatal_error("%s: %s", table_path.c_str(), spx_last_error());
-    const uint64_t min_length = o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
-    const spc_params params{(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty};
-    const spa_params fill{(uint32_t)max_fill};
-    const spe_params ends{(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel};
-    std::fprintf(stderr, "[map] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); a match is an anchor from length %llu on "
-                 "(max-dist %llu, max-gap %llu, gap penalty %llu, lookback %llu, max-fill %llu, max-extend %llu, band %llu, mismatch %llu, "
-                 "indel %llu)\n",
+    const uint64_t min_length = m.min_length(o);
+    const spc_params params = m.chain();
+    const spa_params fill = m.fill();
+    const spe_params ends = m.ends();
+    std::fprintf(stderr, "[map] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); %s\n",
                  (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
-                 (unsigned long long)min_length, max_dist, max_gap, gap_penalty, lookback, max_fill, max_extend, band, mismatch, indel);
+                 m.describe(min_length).c_str());
 
     LinesFile out;
     out.open(o.pattern_file + ".paf", false);
@@ -150,9 +113,7 @@ int map_main(int argc, char** argv) {
             recs.resize(b.take + 1);
             op_offs.assign(b.take + 1, 0);
             ops.clear();
-            // a super-batch ends with the read that fills it, and short reads are many: calls of at most one piece each
-            for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
-                for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+            for_each_piece(b, [&](size_t q0, size_t q1) {
                 uint64_t n = 0;
                 if (map_begin(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
                               o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0, recs.data() + q0, &n) != SPX_OK)
@@ -165,7 +126,7 @@ int map_main(int argc, char** argv) {
                 for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
                 // (without digestion a read's values are its characters)
                 for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
-            }
+            });
         },
         [&](const ReadBatch& b, size_t i) {
             num_reads++;

@@ -1,4 +1,4 @@
-// read_command.cpp -- the driver under `spumoni assign`, `mems` and `place` (read_command.hpp).
+// read_command.cpp -- the driver under `spumoni assign`, `mems`, `place` and the chain family (read_command.hpp).
 #include "read_command.hpp"
 
 #include <dlfcn.h>
@@ -142,6 +142,76 @@ uint64_t null_db_threshold(const ReadOptions& o) {
     return max_value_threshold(percentile, !o.ms, o.use_promotions, o.use_dna_letters);
 }
 
+unsigned long long count_argument(const char* arg) { return arg[0] == '-' ? ~0ull : std::strtoull(arg, nullptr, 10); }
+
+namespace {
+struct MapOption {
+    char c;
+    const char* name;
+    MapOptions::Level level;
+    unsigned long long MapOptions::*value;
+    unsigned long long lo, hi;
+    const char* what;
+};
+const MapOption MAP_OPTIONS[] = {
+    {'S', "max-dist", MapOptions::CHAIN, &MapOptions::max_dist, 1, 2147483647ull, "largest distance"},
+    {'G', "max-gap", MapOptions::CHAIN, &MapOptions::max_gap, 0, 2147483647ull, "largest gap"},
+    {'B', "gap-penalty", MapOptions::CHAIN, &MapOptions::gap_penalty, 0, 65535, "gap penalty"},
+    {'H', "lookback", MapOptions::CHAIN, &MapOptions::lookback, 1, 64, "lookback"},
+    {'F', "max-fill", MapOptions::FILL, &MapOptions::max_fill, 1, 4096, "largest filled gap"},
+    {'E', "max-extend", MapOptions::EXTEND, &MapOptions::max_extend, 1, 4096, "largest extended end"},
+    {'O', "band", MapOptions::EXTEND, &MapOptions::band, 0, 63, "band"},
+    {'N', "mismatch", MapOptions::EXTEND, &MapOptions::mismatch, 0, 65535, "mismatch cost"},
+    {'I', "indel", MapOptions::EXTEND, &MapOptions::indel, 0, 65535, "indel cost"},
+};
+}  // namespace
+
+std::string MapOptions::shorts(const char* own) const {
+    std::string s = "L:";
+    for (const MapOption& m : MAP_OPTIONS)
+        if (m.level <= level) s += std::string(1, m.c) + ":";
+    return s + own;
+}
+std::vector<struct option> MapOptions::longs(const std::vector<struct option>& own) const {
+    std::vector<struct option> t = {{"min-length", required_argument, NULL, 'L'}};
+    for (const MapOption& m : MAP_OPTIONS)
+        if (m.level <= level) t.push_back({m.name, required_argument, NULL, m.c});
+    t.insert(t.end(), own.begin(), own.end());
+    return t;
+}
+bool MapOptions::set(ReadOptions& o, int c, const char* arg) {
+    if (c == 'L') {
+        o.have_threshold = true;
+        o.threshold = std::strtoull(arg, nullptr, 10);
+        return true;
+    }
+    for (const MapOption& m : MAP_OPTIONS)
+        if (m.level <= level && m.c == c) {
+            this->*m.value = count_argument(arg);
+            return true;
+        }
+    return false;
+}
+void MapOptions::validate(const ReadOptions& o) const {
+    if (o.have_threshold && o.threshold == 0) fatal_warning("the minimum match length (-L) must be at least 1.");
+    for (const MapOption& m : MAP_OPTIONS)
+        if (m.level <= level && (this->*m.value < m.lo || this->*m.value > m.hi))
+            fatal_warning("the %s (-%c) must be between %llu and %llu.", m.what, m.c, m.lo, m.hi);
+}
+uint64_t MapOptions::min_length(const ReadOptions& o) const {
+    return o.have_threshold ? o.threshold : std::max<uint64_t>(1, null_db_threshold(o));
+}
+std::string MapOptions::describe(uint64_t min_length) const {
+    std::string s = "a match is an anchor from length " + std::to_string(min_length) + " on (max-dist " + std::to_string(max_dist) +
+                    ", max-gap " + std::to_string(max_gap) + ", gap penalty " + std::to_string(gap_penalty) + ", lookback " +
+                    std::to_string(lookback);
+    if (level >= FILL) s += ", max-fill " + std::to_string(max_fill);
+    if (level >= EXTEND)
+        s += ", max-extend " + std::to_string(max_extend) + ", band " + std::to_string(band) + ", mismatch " + std::to_string(mismatch) +
+             ", indel " + std::to_string(indel);
+    return s + ")";
+}
+
 // name<TAB>length<TAB>text_start<TAB>strands per line (spumoni_amd/map.py: read_seq_table)
 SeqTable read_seq_table(const std::string& path) {
     std::ifstream in(path, std::ios::binary);
@@ -271,6 +341,13 @@ void scan_reads(ReadRun& run, LinesFile& out, const std::function<void(ReadBatch
         fatal_warning("%s was empty after digestion, commonly due to reads "
                       "consisting of mostly non-ACGT characters. Please remove "
                       "read or run SPUMONI without minimizer digestion.", deferred_msg.data());
+    }
+}
+
+void for_each_piece(const ReadBatch& b, const std::function<void(size_t, size_t)>& call) {
+    for (size_t q0 = 0, q1; q0 < b.take; q0 = q1) {
+        for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
+        call(q0, q1);
     }
 }
 

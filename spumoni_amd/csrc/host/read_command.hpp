@@ -1,9 +1,10 @@
-// read_command.hpp -- what `spumoni assign`, `mems` and `place` share: a command that walks the reads of a FASTA / FASTQ
-// file through one product of the device library and writes lines in input order.  The shared options and their rules
-// (`run`'s messages where the rule is the same, spumoni_main.cpp: validate), the look-up of the product's entry points,
-// the run's set-up -- one device (the first of SPUMONI_GPUS), the reads from reads.cpp, the index through the loaders `run`
-// uses --, the loop over super-batches of SPUMONI_SUPER_BATCH characters, and the output file.  A command keeps its usage
-// text, its own options and checks, its call into the library, its lines and its closing line on stderr.
+// read_command.hpp -- what `spumoni assign`, `mems`, `place` and the chain family (`chain` .. `call`) share: a command that
+// walks the reads of a FASTA / FASTQ file through one product of the device library and writes lines in input order.  The
+// shared options and their rules (`run`'s messages where the rule is the same, spumoni_main.cpp: validate), the look-up of
+// the product's entry points, the run's set-up -- one device (the first of SPUMONI_GPUS), the reads from reads.cpp, the
+// index through the loaders `run` uses --, the loop over super-batches of SPUMONI_SUPER_BATCH characters, and the output
+// file.  A command keeps its usage text, its own options and checks, its call into the library, its lines and its closing
+// line on stderr.
 #pragma once
 #include <getopt.h>
 
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/spumoni_extend.h"
 #include "classify.hpp"
 #include "reads.hpp"
 
@@ -65,6 +67,29 @@ struct LinesFile {
     void close();
 };
 
+// The mapping options of `chain` (-L -S -G -B -H), of `align` and `cigar` (FILL: -F on top) and of `extend`, `map`, `cover` and
+// `call` (EXTEND: -E -O -N -I on top of those), with their defaults: the option tables for parse_read_options, the setter
+// for its `extra` (false: not one of these), the range checks in the order of the options, the parameters for the library
+// and the "index loaded" line from "a match is an anchor" to the closing parenthesis.
+struct MapOptions {
+    enum Level { CHAIN, FILL, EXTEND };
+    explicit MapOptions(Level l) : level(l) {}
+    Level level;
+    unsigned long long max_dist = 5000, max_gap = 500, gap_penalty = 1, lookback = 64, max_fill = 512;
+    unsigned long long max_extend = 512, band = 16, mismatch = 4, indel = 6;
+    std::string shorts(const char* own = "") const;  // ... with the command's own behind them
+    std::vector<struct option> longs(const std::vector<struct option>& own = {}) const;
+    bool set(ReadOptions& o, int c, const char* arg);
+    void validate(const ReadOptions& o) const;
+    uint64_t min_length(const ReadOptions& o) const;  // -L, or the null database's threshold (o.ms set, the index's prefix known)
+    spc_params chain() const { return {(uint32_t)lookback, (uint32_t)max_dist, (uint32_t)max_gap, (uint32_t)gap_penalty}; }
+    spa_params fill() const { return {(uint32_t)max_fill}; }
+    spe_params ends() const { return {(uint32_t)max_extend, (uint32_t)band, (uint32_t)mismatch, (uint32_t)indel}; }
+    std::string describe(uint64_t min_length) const;
+};
+// an option's count: a leading '-' is out of every range
+unsigned long long count_argument(const char* arg);
+
 // <prefix>.fa.seqs, the table `spumoni build -s` writes (`map`, `cover`): ends the process on a malformed table
 struct SeqTable {
     std::vector<std::string> names;
@@ -84,5 +109,9 @@ struct ReadBatch {
 // reads in front of it are flushed and the file is closed first, else nothing more is flushed.  Closes `out`.
 void scan_reads(ReadRun& run, LinesFile& out, const std::function<void(ReadBatch&)>& query,
                 const std::function<void(const ReadBatch&, size_t)>& line);
+
+// A super-batch ends with the read that fills it, and short reads are many: `call(q0, q1)` for pieces [q0, q1) of at most
+// 4 Mi reads and 32 Mi characters, one piece of the staged walk each
+void for_each_piece(const ReadBatch& b, const std::function<void(size_t, size_t)>& call);
 
 }  // namespace spumoni_host

@@ -40,11 +40,6 @@ struct AlignArgs {
     AlignCounters* c;
 };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
 // A read's chain record and what the offsets say, checked: the same in the count and in the walk.
 struct ChainOf {
     uint4 w0, w1, w2;

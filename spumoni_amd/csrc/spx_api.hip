@@ -567,7 +567,7 @@ int spx_set_option(spx_index* ix, const char* key, int64_t value) {
             set_error("cover_switch must be between 0 and 2^31 - 1");
             return SPX_E_ARG;
         }
-        ix->cover_switch = (int)value;
+        ix->cover.sw = (int)value;
         return SPX_OK;
     }
     if (!strcmp(key, "call_switch")) {  // spx_call.hip: the same for the pileup's add
@@ -575,7 +575,7 @@ int spx_set_option(spx_index* ix, const char* key, int64_t value) {
             set_error("call_switch must be between 0 and 2^31 - 1");
             return SPX_E_ARG;
         }
-        ix->call_switch = (int)value;
+        ix->call.sw = (int)value;
         return SPX_OK;
     }
     if (!strcmp(key, "minimizer_charhash")) {

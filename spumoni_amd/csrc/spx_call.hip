@@ -16,23 +16,20 @@
 //            finds its first sequence by a search in P and walks on across the borders; a position whose depth passes
 //            min_depth costs one 16-byte load of alt and one byte of text.
 //
+// The sequence table, the tiles, the head of a mapping with its checks and the host code that works on the index's
+// GenomeAcc are spx_genome_kernels.h's, shared by the coverage and the pileup.
+//
 // Control flow: every shuffle and ballot of k_call_add_wave stands in a loop whose trip count is the same for the whole
 // wavefront (the list's length, the read's entries in steps of 64, the long 'X' entries of a step by their ballot) or
 // behind them; the other kernels shuffle and synchronise only outside their loops.
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
-#include <cstring>
 #include <vector>
 
 #include "../../include/spumoni_call.h"
-#include "spx_internal.h"
+#include "spx_genome_kernels.h"
 
 namespace spx {
 namespace {
 
-constexpr uint32_t OP_I = SPG_OP_I, OP_D = SPG_OP_D, OP_N = SPG_OP_N, OP_S = SPE_OP_S, OP_EQ = SPG_OP_EQ, OP_X = SPG_OP_X;
-constexpr int PER_THREAD = 16, TILE = 256 * PER_THREAD;  // positions of a calls tile
 constexpr uint32_t SPREAD = 16;  // an 'X' entry of more columns is spread over the wavefront
 
 struct AddCounters {  // device; zeroed in front of every launch
@@ -51,12 +48,6 @@ struct CallCounters {
 };
 constexpr int CALL_WORDS = sizeof(CallCounters) / 8;
 
-struct Table {
-    const uint64_t* P;  // n_seqs * strands + 1
-    uint64_t n_seqs;
-    uint32_t strands;
-    uint64_t G;
-};
 struct AddArgs {
     Table t;
     const uint4* map;       // 3 per read: spn_mapping
@@ -84,81 +75,21 @@ struct CallArgs {
     const uint32_t* del;
     uint32_t min_depth, min_alt, min_permille;
     uint64_t cap, ntiles;
-    uint4* calls;     // 3 per record: spl_call
+    uint4* rec;       // 3 per record: spl_call
     uint64_t* tcnt;   // ntiles + 1: calls in a tile, then a 0
     uint64_t* toffs;  // ntiles + 1
     uint64_t* count;
     CallCounters* c;
 };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-__device__ inline unsigned long long wave_min(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long o = __shfl_xor(v, s);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ inline unsigned long long wave_max(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long o = __shfl_xor(v, s);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ inline bool in_text(uint32_t op) { return op == OP_EQ || op == OP_X || op == OP_D || op == OP_N; }
-__device__ inline bool in_read(uint32_t op) { return op == OP_EQ || op == OP_X || op == OP_I || op == OP_S; }
-__device__ inline bool is_op(uint32_t op) { return in_text(op) || op == OP_I || op == OP_S; }
-__device__ inline uint64_t seq_start(const Table& t, uint64_t s) { return t.P[s * t.strands] / t.strands; }  // s <= n_seqs
-// the sequence that holds position x < G of the forward genome
-__device__ inline uint64_t seq_of(const Table& t, uint64_t x) {
-    uint64_t lo = 0, hi = t.n_seqs;  // F[lo] <= x < F[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (seq_start(t, mid) <= x)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 // 0 .. 3 for A/a, C/c, G/g, T/t, 4 for every other byte
 __device__ inline uint32_t code_of(uint8_t b) {
     const uint32_t u = b & 0xdfu;  // (only 'a' .. 'z' land on 'A' .. 'Z')
     return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
 }
 
-struct ReadHead {
-    uint32_t s;
-    bool rev;
-    uint64_t pos, span, i0, ne, r0, len;  // pos: F[s] + target_start; span: target_end - target_start
-};
-// 0: unmapped, 1: the record and the offsets pass, 2: they do not
-__device__ inline int read_head(const AddArgs& a, uint64_t q, ReadHead& h) {
-    const uint4 w1 = a.map[3 * q + 1];
-    if (w1.x == SPN_UNMAPPED) return 0;
-    const uint4 w0 = a.map[3 * q];
-    const uint64_t ts = (uint64_t)w0.x | ((uint64_t)w0.y << 32), te = (uint64_t)w0.z | ((uint64_t)w0.w << 32);
-    const uint64_t i0 = a.ioffs[q], i1 = a.ioffs[q + 1], r0 = a.roffs[q], r1 = a.roffs[q + 1];
-    if (w1.x >= a.t.n_seqs || i1 < i0 || i1 > a.in_entries || r1 < r0 || r1 > a.in_chars || ts > te) return 2;
-    const uint64_t p0 = a.t.P[(uint64_t)w1.x * a.t.strands], p1 = a.t.P[(uint64_t)w1.x * a.t.strands + 1];
-    if (te > p1 - p0) return 2;
-    h.s = w1.x;
-    h.rev = w1.y != 0;
-    h.pos = p0 / a.t.strands + ts;
-    h.span = te - ts;
-    h.i0 = i0;
-    h.ne = i1 - i0;
-    h.r0 = r0;
-    h.len = r1 - r0;
-    return 1;
-}
-
 // One 'X' column of a checked read: g < F[s] + target_end <= G, j < len.  1 when the column's code is 4.
-__device__ inline unsigned long long add_column(const AddArgs& a, const ReadHead& h, uint64_t g, uint64_t j) {
+__device__ inline unsigned long long add_column(const AddArgs& a, const MapHead& h, uint64_t g, uint64_t j) {
     uint32_t c = code_of(a.reads[h.r0 + (h.rev ? h.len - 1 - j : j)]);
     if (c == 4) {
         atomicAdd(a.other + g, 1u);
@@ -169,29 +100,13 @@ __device__ inline unsigned long long add_column(const AddArgs& a, const ReadHead
     return 0;
 }
 
-// N sums leave a block of four wavefronts as one set of atomics
-template <int N>
-__device__ inline void block_counts(unsigned long long* part, unsigned long long* to, unsigned long long (&v)[N]) {
-    const uint32_t wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const unsigned long long s = wave_sum(v[i]);
-        if ((threadIdx.x & 63) == 0) part[wv * N + i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        const unsigned long long s = part[threadIdx.x] + part[N + threadIdx.x] + part[2 * N + threadIdx.x] + part[3 * N + threadIdx.x];
-        if (s) atomicAdd(to + threadIdx.x, s);
-    }
-}
-
 // A lane per read, a block over a stride of reads.
 __global__ __launch_bounds__(256) void k_call_add_lane(AddArgs a) {
     __shared__ unsigned long long part[4 * 7];
     unsigned long long mapped = 0, added = 0, skipped = 0, xcols = 0, others = 0, nins = 0, ndel = 0;
     for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < a.nreads; q += (uint64_t)gridDim.x * 256) {
-        ReadHead h;
-        const int st = read_head(a, q, h);
+        MapHead h;
+        const int st = map_head<true>(a, q, h);
         if (st == 0) continue;
         mapped += 1;
         if (st == 2) {
@@ -266,8 +181,8 @@ __global__ __launch_bounds__(256) void k_call_add_wave(AddArgs a) {
     const uint32_t lane = threadIdx.x & 63;
     unsigned long long added = 0, skipped = 0, xcols = 0, others = 0, nins = 0, ndel = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < nlong; i += (uint64_t)gridDim.x * 4) {
-        ReadHead h;
-        if (read_head(a, a.longs[i], h) != 1) continue;  // (the lane's kernel listed it because it is 1; the same for every lane)
+        MapHead h;
+        if (map_head<true>(a, a.longs[i], h) != 1) continue;  // (the lane's kernel listed it because it is 1; the same for every lane)
         const uint32_t* src = a.iops + h.i0;
         // pass 1: each lane over its entries, the sums behind the loop.  No 'S' between two others: the entries that are
         // not 'S' are as many as lie between the first and the last of them.  No 'I' behind the last text column: the
@@ -384,9 +299,8 @@ __device__ inline uint32_t scan_calls(const CallArgs& a, uint64_t p0, uint64_t p
 __global__ __launch_bounds__(256) void k_call_count(CallArgs a) {
     using Reduce = hipcub::BlockReduce<uint32_t, 256>;
     __shared__ typename Reduce::TempStorage tmp;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TILE, t1 = t0 + TILE < a.t.G ? t0 + TILE : a.t.G;
-    const uint64_t p0 = t0 + (uint64_t)threadIdx.x * PER_THREAD, p1 = p0 + PER_THREAD < t1 ? p0 + PER_THREAD : t1;
-    const uint32_t mine = scan_calls(a, p0, p1, [](uint64_t, uint32_t, uint32_t, const uint4&, uint8_t, uint32_t, uint64_t) {});
+    const Tile x = tile_of(a.t.G);
+    const uint32_t mine = scan_calls(a, x.p0, x.p1, [](uint64_t, uint32_t, uint32_t, const uint4&, uint8_t, uint32_t, uint64_t) {});
     const uint32_t n = Reduce(tmp).Sum(mine);
     if (threadIdx.x == 0) {
         a.tcnt[blockIdx.x] = n;
@@ -397,43 +311,29 @@ __global__ __launch_bounds__(256) void k_call_count(CallArgs a) {
 __global__ __launch_bounds__(256) void k_call_write(CallArgs a) {
     using Scan = hipcub::BlockScan<uint32_t, 256>;
     __shared__ typename Scan::TempStorage tmp;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TILE, t1 = t0 + TILE < a.t.G ? t0 + TILE : a.t.G;
-    const uint64_t p0 = t0 + (uint64_t)threadIdx.x * PER_THREAD, p1 = p0 + PER_THREAD < t1 ? p0 + PER_THREAD : t1;
+    const Tile x = tile_of(a.t.G);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const uint64_t total = a.toffs[a.ntiles];
         *a.count = total;
         a.c->calls = total;
         if (total > a.cap) atomicOr(&a.c->error, 2ull);
     }
-    const uint32_t mine = scan_calls(a, p0, p1, [](uint64_t, uint32_t, uint32_t, const uint4&, uint8_t, uint32_t, uint64_t) {});
+    const uint32_t mine = scan_calls(a, x.p0, x.p1, [](uint64_t, uint32_t, uint32_t, const uint4&, uint8_t, uint32_t, uint64_t) {});
     uint32_t before = 0;
     Scan(tmp).ExclusiveSum(mine, before);
     if (!mine) return;
     uint64_t next = a.toffs[blockIdx.x] + before;
-    scan_calls(a, p0, p1, [&](uint64_t at, uint32_t s, uint32_t d, const uint4& al, uint8_t ref, uint32_t allele, uint64_t p) {
+    scan_calls(a, x.p0, x.p1, [&](uint64_t at, uint32_t s, uint32_t d, const uint4& al, uint8_t ref, uint32_t allele, uint64_t p) {
         const uint64_t r = next++;
         if (r >= a.cap) return;
-        a.calls[3 * r] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), s, d);
-        a.calls[3 * r + 1] = al;
-        a.calls[3 * r + 2] = make_uint4(a.other[p], a.del[p], a.ins[p], (uint32_t)ref | (allele << 8));
+        a.rec[3 * r] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), s, d);
+        a.rec[3 * r + 1] = al;
+        a.rec[3 * r + 2] = make_uint4(a.other[p], a.del[p], a.ins[p], (uint32_t)ref | (allele << 8));
     });
 }
 
-int need_table(const spx_index* ix, const char* who) {
-    if (!ix) {
-        set_error("index must be non-null");
-        return SPX_E_ARG;
-    }
-    if (!ix->map_P) {
-        set_error("%s needs the sequence table: the index has none (spn_set_sequences; spumoni build -s writes it)", who);
-        return SPX_E_ARG;
-    }
-    return SPX_OK;
-}
-Table table_of(const spx_index* ix) {
-    return Table{ix->map_P, ix->map_seq_lengths.size(), ix->map_strands, ix->n_text / ix->map_strands};
-}
-uint64_t tiles_of(uint64_t G) { return (G + TILE - 1) / TILE; }
+constexpr GenomeKind KIND = {"spl_call_reset", "the pileup", "about 28 per base beside the coverage's 12", "spl_calls_begin", "spl_calls_fetch",
+                             "out_calls", {ADD_WORDS, FIN_WORDS, CALL_WORDS}, 8, sizeof(spl_call)};
 
 int check_params(uint32_t min_depth, uint32_t min_alt, uint32_t min_permille) {
     if (min_depth < 1 || min_alt < 1 || min_permille > 1000) {
@@ -444,113 +344,31 @@ int check_params(uint32_t min_depth, uint32_t min_alt, uint32_t min_permille) {
     return SPX_OK;
 }
 
-void add_reset(spx_index* ix) {
-    product_reset(ix, ix->call_add);
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->call_acc, 0, sizeof ix->call_acc);
+int call_add_enqueue(spx_index* ix, AddArgs& a, hipStream_t st) { return add_enqueue(ix, ix->call, KIND, a, st, k_call_add_lane, k_call_add_wave); }
+
+// hipcub's inclusive sum over ddiff gives del
+int call_finish_enqueue(spx_index* ix, const uint32_t* d_ddiff, uint32_t* d_del, hipStream_t st) {
+    return finish_enqueue(ix, ix->call, KIND, d_ddiff, d_del, st, [](const Table&) { return SPX_OK; });
 }
 
-// The list of one call and both kernels on st, between the step's two events.  Takes ix->mu.
-int add_enqueue(spx_index* ix, AddArgs& a, hipStream_t st) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    a.t = table_of(ix);
-    a.sw = (uint64_t)ix->call_switch;
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->call_scr[spx_index::PL_LONG].reserve(a.nreads * 8 + 8, &p)) != SPX_OK) return rc;
-    a.longs = (uint64_t*)p;
-    return product_enqueue(ix->call_add, ADD_WORDS, st, [&](void* counters) -> int {
-        a.c = (AddCounters*)counters;
-        if (!a.nreads) return SPX_OK;
-        const unsigned grid = (unsigned)std::min<uint64_t>((a.nreads + 255) / 256, 1024);
-        k_call_add_lane<<<grid, 256, 0, st>>>(a);
-        SPX_HIP(hipGetLastError());
-        k_call_add_wave<<<(unsigned)std::min<uint64_t>((a.nreads + 3) / 4, 2048), 256, 0, st>>>(a);
-        SPX_HIP(hipGetLastError());
-        return SPX_OK;
-    });
-}
-
-int finish_enqueue(spx_index* ix, const uint32_t* d_ddiff, uint32_t* d_del, hipStream_t st) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    const uint64_t G = table_of(ix).G;
-    size_t cub_bytes = 0;
-    SPX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, cub_bytes, d_ddiff, d_del, G, (hipStream_t) nullptr));
-    void* cub = nullptr;
-    int rc;
-    if ((rc = ix->call_scr[spx_index::PL_CUB].reserve(cub_bytes + 16, &cub)) != SPX_OK) return rc;
-    return product_enqueue(ix->call_fin, FIN_WORDS, st, [&](void*) -> int {
-        SPX_HIP(hipcub::DeviceScan::InclusiveSum(cub, cub_bytes, d_ddiff, d_del, G, st));
-        return SPX_OK;
-    });
-}
-
-// count without write: the tiles' counts and their scan only; write without count: the second half of the host form,
-// which sizes its records from the count before it writes them
 int calls_enqueue(spx_index* ix, CallArgs& a, hipStream_t st, bool count, bool write) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    a.t = table_of(ix);
-    a.text = ix->text;
-    a.ntiles = tiles_of(a.t.G);
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->call_scr[spx_index::PL_TCNT].reserve((a.ntiles + 1) * 8, &p)) != SPX_OK) return rc;
-    a.tcnt = (uint64_t*)p;
-    if ((rc = ix->call_scr[spx_index::PL_TOFFS].reserve((a.ntiles + 1) * 8, &p)) != SPX_OK) return rc;
-    a.toffs = (uint64_t*)p;
-    size_t cub_bytes = 0;
-    SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, a.tcnt, a.toffs, a.ntiles + 1, (hipStream_t) nullptr));
-    void* cub = nullptr;
-    if ((rc = ix->call_scr[spx_index::PL_CUB2].reserve(cub_bytes + 16, &cub)) != SPX_OK) return rc;
-    auto launch = [&](void* counters) -> int {
-        a.c = (CallCounters*)counters;
-        if (count) {
+    // (the callables run under ix->mu, which guards ix->text as it guards the table)
+    return tiles_enqueue(
+        ix, ix->call, KIND, a, st, count, write,
+        [&] {
+            a.text = ix->text;
             k_call_count<<<(unsigned)a.ntiles, 256, 0, st>>>(a);
-            SPX_HIP(hipGetLastError());
-            SPX_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, a.tcnt, a.toffs, a.ntiles + 1, st));
-        }
-        if (write) {
+        },
+        [&]() -> int {
+            a.text = ix->text;
             k_call_write<<<(unsigned)a.ntiles, 256, 0, st>>>(a);
             SPX_HIP(hipGetLastError());
-        }
-        return SPX_OK;
-    };
-    if (count) return product_enqueue(ix->call_calls, CALL_WORDS, st, launch);
-    // the second half of the host form: the same counters, the step's end moved behind the write
-    if ((rc = launch(ix->call_calls.counters.p)) != SPX_OK) return rc;
-    SPX_HIP(hipEventRecord(ix->call_calls.ev1, st));
-    return SPX_OK;
-}
-
-// Waits for what a step enqueued last and takes its counters and its time.  Takes ix->mu.
-int step_collect(spx_index* ix, spx_index::Product& p, int words, int step) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventSynchronize(p.ev1));
-    unsigned long long c[ADD_WORDS] = {};
-    SPX_HIP(hipMemcpy(c, p.counters.p, (size_t)words * 8, hipMemcpyDeviceToHost));
-    SPX_HIP(hipEventElapsedTime(&ix->call_step_ms[step], p.ev0, p.ev1));
-    if (step == 0)
-        for (int i = 0; i < 8; ++i) ix->call_acc[i] += c[i];
-    if (step == 2) ix->call_ncalls = c[0];
-    p.error = step == 2 ? c[words - 1] : p.error | c[words - 1];
-    p.pending = false;
-    return SPX_OK;
-}
-
-int collect_all(spx_index* ix) {
-    int rc;
-    if (ix->call_add.pending && (rc = step_collect(ix, ix->call_add, ADD_WORDS, 0)) != SPX_OK) return rc;
-    if (ix->call_fin.pending && (rc = step_collect(ix, ix->call_fin, FIN_WORDS, 1)) != SPX_OK) return rc;
-    if (ix->call_calls.pending && (rc = step_collect(ix, ix->call_calls, CALL_WORDS, 2)) != SPX_OK) return rc;
-    return SPX_OK;
+            return SPX_OK;
+        });
 }
 
 int add_error_code(const spx_index* ix) {
-    if (ix->call_add.error & 1) {
+    if (ix->call.step[GenomeAcc::ADD].error & 1) {
         set_error("a read failed the pileup's checks (the coverage's checks on its mapping, entries whose read lengths disagree with "
                   "the read's, an 'I' behind the last text column, or read offsets outside the reads): such a read adds nothing");
         return SPX_E_FORMAT;
@@ -558,57 +376,22 @@ int add_error_code(const spx_index* ix) {
     return SPX_OK;
 }
 
-// The host forms' arrays are there and belong to the table in force.  The caller holds host_mu.
-int need_arrays(spx_index* ix, const char* who) {
-    int rc;
-    if ((rc = need_table(ix, who)) != SPX_OK) return rc;
-    if (ix->call_dropped) {
-        set_error("%s: spn_set_sequences replaced the sequence table after spl_call_reset and dropped the pileup: reset again", who);
-        return SPX_E_ARG;
-    }
-    if (!ix->call_G) {
-        set_error("%s without a successful spl_call_reset before it", who);
-        return SPX_E_ARG;
-    }
-    return cover_need_arrays(ix, who);
+// The host forms' arrays of both products are there and belong to the table in force.  The caller holds host_mu.
+int call_need_arrays(spx_index* ix, const char* who) {
+    const int rc = need_arrays(ix, ix->call, KIND, who);
+    return rc != SPX_OK ? rc : cover_need_arrays(ix, who);
+}
+
+template <typename T>
+T* array_of(spx_index* ix, int slot) {
+    return (T*)ix->call.scr[slot].p;
 }
 
 // del from the handle's ddiff, when something was added since it was made.  The caller holds host_mu.
-int finish_host(spx_index* ix) {
-    if (!ix->call_dirty) return SPX_OK;
-    hipStream_t st = nullptr;
-    int rc;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    if ((rc = finish_enqueue(ix, (const uint32_t*)ix->call_scr[spx_index::PL_DDIFF].p, (uint32_t*)ix->call_scr[spx_index::PL_DEL].p, st)) != SPX_OK)
-        return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->call_fin, FIN_WORDS, 1)) != SPX_OK) return rc;
-    ix->call_dirty = false;
-    return SPX_OK;
-}
-
-// exactly `bytes`: the arrays of a genome are not given the scratch buffers' head-room
-int exact(spx_index::Scratch& sc, size_t bytes) {
-    if (sc.cap >= bytes) return SPX_OK;
-    if (sc.p) (void)hipFree(sc.p);
-    sc.p = nullptr;
-    sc.cap = 0;
-    SPX_HIP(hipMalloc(&sc.p, bytes));
-    sc.cap = bytes;
-    return SPX_OK;
-}
-
-constexpr int ARRAYS[5] = {spx_index::PL_ALT, spx_index::PL_OTHER, spx_index::PL_INS, spx_index::PL_DDIFF, spx_index::PL_DEL};
-
-void drop_arrays(spx_index* ix) {
-    for (int i : {spx_index::PL_ALT, spx_index::PL_OTHER, spx_index::PL_INS, spx_index::PL_DDIFF, spx_index::PL_DEL, spx_index::PL_CALLS}) {
-        spx_index::Scratch& sc = ix->call_scr[i];
-        if (sc.p) (void)hipFree(sc.p);
-        sc.p = nullptr;
-        sc.cap = 0;
-    }
-    ix->call_G = 0;
-    ix->call_ready = false;
+int call_finish_host(spx_index* ix) {
+    return finish_host(ix, ix->call, KIND, [&](hipStream_t st) {
+        return call_finish_enqueue(ix, array_of<const uint32_t>(ix, spx_index::PL_DDIFF), array_of<uint32_t>(ix, spx_index::PL_DEL), st);
+    });
 }
 
 // Waits for the copy of a batch's reads when the call that issued it ends, however it ends: the copy reads the caller's
@@ -623,25 +406,12 @@ struct CopyGuard {
 }  // namespace
 
 void release_call(spx_index* ix) {
-    for (auto& sc : ix->call_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    product_release(ix->call_add);
-    product_release(ix->call_fin);
-    product_release(ix->call_calls);
+    release_acc(ix->call);
     if (ix->call_copy_ev) (void)hipEventDestroy(ix->call_copy_ev);
     if (ix->call_copy_s) (void)hipStreamDestroy(ix->call_copy_s);
 }
-
-int clone_call(spx_index* src, spx_index* ix) { return src->call_G ? spl_call_reset(ix) : SPX_OK; }
-
-void call_table_changed(spx_index* ix) {
-    // (a kernel of an earlier call may still read the old table or the arrays)
-    for (spx_index::Product* p : {&ix->call_add, &ix->call_fin, &ix->call_calls})
-        if (p->have && p->ev1) (void)hipEventSynchronize(p->ev1);  // (a reset sets `have` for the stats and creates no event)
-    if (!ix->call_G) return;
-    drop_arrays(ix);
-    ix->call_dropped = true;
-}
+int clone_call(spx_index* src, spx_index* ix) { return src->call.G ? spl_call_reset(ix) : SPX_OK; }
+void call_table_changed(spx_index* ix) { acc_table_changed(ix->call); }
 
 }  // namespace spx
 
@@ -665,7 +435,7 @@ int spl_pileup_add_device(spx_index* ix, const spn_mapping* d_mappings, const ui
                   "8-byte, d_ops, d_other, d_ins and d_ddiff 4-byte aligned");
         return SPX_E_ARG;
     }
-    add_reset(ix);
+    add_reset(ix, ix->call);
     AddArgs a{};
     a.map = (const uint4*)d_mappings;
     a.ioffs = d_op_offsets;
@@ -679,7 +449,7 @@ int spl_pileup_add_device(spx_index* ix, const spn_mapping* d_mappings, const ui
     a.other = d_other;
     a.ins = d_ins;
     a.ddiff = d_ddiff;
-    return add_enqueue(ix, a, (hipStream_t)stream);
+    return call_add_enqueue(ix, a, (hipStream_t)stream);
 }
 
 int spl_pileup_finish_device(spx_index* ix, const uint32_t* d_ddiff, uint32_t* d_del, void* stream) {
@@ -693,7 +463,7 @@ int spl_pileup_finish_device(spx_index* ix, const uint32_t* d_ddiff, uint32_t* d
         set_error("d_ddiff and d_del must be 4-byte aligned");
         return SPX_E_ARG;
     }
-    return finish_enqueue(ix, d_ddiff, d_del, (hipStream_t)stream);
+    return call_finish_enqueue(ix, d_ddiff, d_del, (hipStream_t)stream);
 }
 
 int spl_calls_device(spx_index* ix, const uint32_t* d_depth, const uint32_t* d_mism, const uint32_t* d_alt, const uint32_t* d_other,
@@ -721,7 +491,7 @@ int spl_calls_device(spx_index* ix, const uint32_t* d_depth, const uint32_t* d_m
     a.min_alt = min_alt;
     a.min_permille = min_permille;
     a.cap = call_capacity;
-    a.calls = (uint4*)d_calls;
+    a.rec = (uint4*)d_calls;
     a.count = d_count;
     return calls_enqueue(ix, a, (hipStream_t)stream, true, true);
 }
@@ -732,38 +502,13 @@ int spl_call_reset(spx_index* ix) {
     if ((rc = spd_cover_reset(ix)) != SPX_OK) return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
-    const Table t = table_of(ix);
-    const size_t bytes[5] = {(size_t)t.G * 16, (size_t)t.G * 4, (size_t)t.G * 4, (size_t)(t.G + 1) * 4, (size_t)t.G * 4};
-    size_t need = 0;
-    for (int i = 0; i < 5; ++i)
-        if (ix->call_scr[ARRAYS[i]].cap < bytes[i]) need += bytes[i];
-    size_t free_b = 0, total_b = 0;
-    SPX_HIP(hipMemGetInfo(&free_b, &total_b));
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if (need > free_b) {
-            set_error("spl_call_reset: the pileup of %llu bases needs %llu more bytes of device memory (about 28 per base beside the "
-                      "coverage's 12), %llu are free",
-                      (unsigned long long)t.G, (unsigned long long)need, (unsigned long long)free_b);
-            return SPX_E_UNSUPPORTED;
-        }
-        for (int i = 0; i < 5; ++i)
-            if ((rc = exact(ix->call_scr[ARRAYS[i]], bytes[i])) != SPX_OK) {
-                drop_arrays(ix);
-                return rc;
-            }
-    }
-    hipStream_t st = nullptr;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    for (int i = 0; i < 4; ++i) SPX_HIP(hipMemsetAsync(ix->call_scr[ARRAYS[i]].p, 0, bytes[i], st));
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    add_reset(ix);
-    ix->call_G = t.G;
-    ix->call_dropped = false;
-    ix->call_dirty = true;
-    ix->call_ready = false;
-    ix->call_add.have = true;  // (the stats of no adds are zeros)
-    return SPX_OK;
+    const size_t G = table_of(ix).G;
+    return reset_arrays(ix, ix->call, KIND, G,
+                        {{spx_index::PL_ALT, G * 16, true},
+                         {spx_index::PL_OTHER, G * 4, true},
+                         {spx_index::PL_INS, G * 4, true},
+                         {spx_index::PL_DDIFF, (G + 1) * 4, true},
+                         {spx_index::PL_DEL, G * 4, false}});
 }
 
 int spl_call_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets, uint64_t nreads,
@@ -780,7 +525,7 @@ int spl_call_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, c
     void *d_reads = nullptr, *d_roffs = nullptr;
     {
         std::lock_guard<std::mutex> hg(ix->host_mu);
-        if ((rc = need_arrays(ix, "spl_call_add_batch")) != SPX_OK) return rc;
+        if ((rc = call_need_arrays(ix, "spl_call_add_batch")) != SPX_OK) return rc;
         bool sorted = seqs && offsets && nreads;
         for (uint64_t q = 0; sorted && q < nreads; ++q) sorted = offsets[q] <= offsets[q + 1];
         if (sorted) {
@@ -789,8 +534,8 @@ int spl_call_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, c
             for (uint64_t q = 0; q <= nreads; ++q) rel[q] = offsets[q] - offsets[0];
             std::lock_guard<std::mutex> g(ix->mu);
             SPX_HIP(hipSetDevice(ix->device));
-            if ((rc = ix->call_scr[spx_index::PL_READS].reserve(chars + 16, &d_reads)) != SPX_OK) return rc;
-            if ((rc = ix->call_scr[spx_index::PL_ROFFS].reserve((nreads + 1) * 8, &d_roffs)) != SPX_OK) return rc;
+            if ((rc = ix->call.scr[spx_index::PL_READS].reserve(chars + 16, &d_reads)) != SPX_OK) return rc;
+            if ((rc = ix->call.scr[spx_index::PL_ROFFS].reserve((nreads + 1) * 8, &d_roffs)) != SPX_OK) return rc;
             if (!ix->call_copy_s) SPX_HIP(hipStreamCreateWithFlags(&ix->call_copy_s, hipStreamNonBlocking));
             if (!ix->call_copy_ev) SPX_HIP(hipEventCreateWithFlags(&ix->call_copy_ev, hipEventDisableTiming));
             guard.s = ix->call_copy_s;
@@ -803,7 +548,7 @@ int spl_call_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, c
     rc = cover_add_batch_with(ix, "spl_call_add_batch", digest_kind, k, w, seqs, offsets, nreads, min_length, want_docs, chain_params,
                               align_params, extend_params, out_mappings, [&](const CoverBatch& b) -> int {
                                   int rc2;
-                                  if ((rc2 = need_arrays(ix, "spl_call_add_batch")) != SPX_OK) return rc2;
+                                  if ((rc2 = call_need_arrays(ix, "spl_call_add_batch")) != SPX_OK) return rc2;
                                   if (!copied) {
                                       set_error("spl_call_add_batch: the reads' offsets decrease");
                                       return SPX_E_ARG;
@@ -818,17 +563,17 @@ int spl_call_add_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, c
                                   a.reads = (const uint8_t*)d_reads;
                                   a.roffs = (const uint64_t*)d_roffs;
                                   a.in_chars = chars;
-                                  a.alt = (uint32_t*)ix->call_scr[spx_index::PL_ALT].p;
-                                  a.other = (uint32_t*)ix->call_scr[spx_index::PL_OTHER].p;
-                                  a.ins = (uint32_t*)ix->call_scr[spx_index::PL_INS].p;
-                                  a.ddiff = (uint32_t*)ix->call_scr[spx_index::PL_DDIFF].p;
-                                  ix->call_dirty = true;
-                                  ix->call_ready = false;
-                                  return add_enqueue(ix, a, b.stream);
+                                  a.alt = array_of<uint32_t>(ix, spx_index::PL_ALT);
+                                  a.other = array_of<uint32_t>(ix, spx_index::PL_OTHER);
+                                  a.ins = array_of<uint32_t>(ix, spx_index::PL_INS);
+                                  a.ddiff = array_of<uint32_t>(ix, spx_index::PL_DDIFF);
+                                  ix->call.dirty = true;
+                                  ix->call.ready = false;
+                                  return call_add_enqueue(ix, a, b.stream);
                               });
     std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (ix->call_add.pending) {  // (enqueued: the coverage's wait may or may not have come behind it)
-        const int rc2 = step_collect(ix, ix->call_add, ADD_WORDS, 0);
+    if (ix->call.step[GenomeAcc::ADD].pending) {  // (enqueued: the coverage's wait may or may not have come behind it)
+        const int rc2 = step_collect(ix, ix->call, KIND, GenomeAcc::ADD);
         if (rc == SPX_OK) rc = rc2;
     }
     return rc != SPX_OK ? rc : add_error_code(ix);
@@ -842,64 +587,27 @@ int spl_calls_begin(spx_index* ix, uint32_t min_depth, uint32_t min_alt, uint32_
     *n_calls = 0;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     int rc;
-    if ((rc = need_arrays(ix, "spl_calls_begin")) != SPX_OK) return rc;
+    if ((rc = call_need_arrays(ix, "spl_calls_begin")) != SPX_OK) return rc;
     if ((rc = check_params(min_depth, min_alt, min_permille)) != SPX_OK) return rc;
-    SPX_HIP(hipSetDevice(ix->device));
-    ix->call_ready = false;
-    if ((rc = cover_finish_host(ix)) != SPX_OK) return rc;
-    if ((rc = finish_host(ix)) != SPX_OK) return rc;
-    hipStream_t st = nullptr;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    void* d_n = nullptr;
-    if ((rc = ix->call_scr[spx_index::PL_NCALLS].reserve(8, &d_n)) != SPX_OK) return rc;
     CallArgs a{};
-    a.depth = (const uint32_t*)ix->cover_scr[spx_index::D_DEPTH].p;
-    a.alt = (const uint4*)ix->call_scr[spx_index::PL_ALT].p;
-    a.other = (const uint32_t*)ix->call_scr[spx_index::PL_OTHER].p;
-    a.ins = (const uint32_t*)ix->call_scr[spx_index::PL_INS].p;
-    a.del = (const uint32_t*)ix->call_scr[spx_index::PL_DEL].p;
+    a.depth = (const uint32_t*)ix->cover.scr[spx_index::D_DEPTH].p;
+    a.alt = array_of<const uint4>(ix, spx_index::PL_ALT);
+    a.other = array_of<const uint32_t>(ix, spx_index::PL_OTHER);
+    a.ins = array_of<const uint32_t>(ix, spx_index::PL_INS);
+    a.del = array_of<const uint32_t>(ix, spx_index::PL_DEL);
     a.min_depth = min_depth;
     a.min_alt = min_alt;
     a.min_permille = min_permille;
-    a.count = (uint64_t*)d_n;
-    // count, the one wait of the calls' own, the records at their exact size, write
-    if ((rc = calls_enqueue(ix, a, st, true, false)) != SPX_OK) return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    uint64_t total = 0;
-    SPX_HIP(hipMemcpy(&total, a.toffs + a.ntiles, 8, hipMemcpyDeviceToHost));
-    void* d_calls = nullptr;
-    if ((rc = ix->call_scr[spx_index::PL_CALLS].reserve(total * sizeof(spl_call) + 48, &d_calls)) != SPX_OK) return rc;
-    a.calls = (uint4*)d_calls;
-    a.cap = total;
-    if ((rc = calls_enqueue(ix, a, st, false, true)) != SPX_OK) return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->call_calls, CALL_WORDS, 2)) != SPX_OK) return rc;
-    ix->call_ready = true;
-    ix->call_ready_n = total;
-    *n_calls = total;
-    return SPX_OK;
+    return records_begin(
+        ix, ix->call, KIND, a, n_calls,
+        [&] {
+            const int rc2 = cover_finish_host(ix);
+            return rc2 != SPX_OK ? rc2 : call_finish_host(ix);
+        },
+        [&](CallArgs& c, hipStream_t st, bool count, bool write) { return calls_enqueue(ix, c, st, count, write); });
 }
 
-int spl_calls_fetch(spx_index* ix, spl_call* out_calls) {
-    if (!ix) {
-        set_error("index must be non-null");
-        return SPX_E_ARG;
-    }
-    std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (!ix->call_ready) {
-        set_error("spl_calls_fetch without a successful spl_calls_begin before it");
-        return SPX_E_ARG;
-    }
-    if (ix->call_ready_n && !out_calls) {
-        set_error("out_calls must be non-null");
-        return SPX_E_ARG;
-    }
-    ix->call_ready = false;
-    if (!ix->call_ready_n) return SPX_OK;
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipMemcpy(out_calls, ix->call_scr[spx_index::PL_CALLS].p, ix->call_ready_n * sizeof(spl_call), hipMemcpyDeviceToHost));
-    return SPX_OK;
-}
+int spl_calls_fetch(spx_index* ix, spl_call* out_calls) { return records_fetch(ix, &spx_index::call, KIND, out_calls); }
 
 int spl_pileup_counts(spx_index* ix, uint64_t first, uint64_t count, uint32_t* out_alt, uint32_t* out_other, uint32_t* out_ins,
                       uint32_t* out_del) {
@@ -909,21 +617,16 @@ int spl_pileup_counts(spx_index* ix, uint64_t first, uint64_t count, uint32_t* o
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
     int rc;
-    if ((rc = need_arrays(ix, "spl_pileup_counts")) != SPX_OK) return rc;
-    if (first > ix->call_G || count > ix->call_G - first) {
-        set_error("spl_pileup_counts: [%llu, %llu + %llu) does not lie in the forward genome of %llu bases", (unsigned long long)first,
-                  (unsigned long long)first, (unsigned long long)count, (unsigned long long)ix->call_G);
-        return SPX_E_ARG;
-    }
+    if ((rc = call_need_arrays(ix, "spl_pileup_counts")) != SPX_OK) return rc;
+    if ((rc = check_range(ix->call, "spl_pileup_counts", first, count)) != SPX_OK) return rc;
     SPX_HIP(hipSetDevice(ix->device));
-    if ((rc = finish_host(ix)) != SPX_OK) return rc;
+    if ((rc = call_finish_host(ix)) != SPX_OK) return rc;
     if (!count) return SPX_OK;
     uint32_t* const out[4] = {out_alt, out_other, out_ins, out_del};
     const int slot[4] = {spx_index::PL_ALT, spx_index::PL_OTHER, spx_index::PL_INS, spx_index::PL_DEL};
     for (int i = 0; i < 4; ++i) {
         const uint64_t per = i == 0 ? 4 : 1;
-        if (out[i])
-            SPX_HIP(hipMemcpy(out[i], (const uint32_t*)ix->call_scr[slot[i]].p + first * per, count * per * 4, hipMemcpyDeviceToHost));
+        if (out[i]) SPX_HIP(hipMemcpy(out[i], array_of<const uint32_t>(ix, slot[i]) + first * per, count * per * 4, hipMemcpyDeviceToHost));
     }
     return SPX_OK;
 }
@@ -933,26 +636,27 @@ int spl_last_call_stats(spx_index* ix, spl_call_stats* out) {
         set_error("null argument");
         return SPX_E_ARG;
     }
-    if (!ix->call_add.have && !ix->call_fin.have && !ix->call_calls.have) {
+    if (!have_any(ix->call)) {
         set_error("no pileup has been computed on this index yet");
         return SPX_E_ARG;
     }
-    const int rc = collect_all(ix);
+    const int rc = collect_all(ix, ix->call, KIND);
     if (rc != SPX_OK) return rc;
+    const GenomeAcc& ga = ix->call;
     std::memset(out, 0, sizeof *out);
-    out->reads = ix->call_acc[0];
-    out->mapped = ix->call_acc[1];
-    out->added = ix->call_acc[2];
-    out->skipped = ix->call_acc[3];
-    out->x_columns = ix->call_acc[4];
-    out->other_columns = ix->call_acc[5];
-    out->insertions = ix->call_acc[6];
-    out->deletions = ix->call_acc[7];
+    out->reads = ga.acc[0];
+    out->mapped = ga.acc[1];
+    out->added = ga.acc[2];
+    out->skipped = ga.acc[3];
+    out->x_columns = ga.acc[4];
+    out->other_columns = ga.acc[5];
+    out->insertions = ga.acc[6];
+    out->deletions = ga.acc[7];
     out->atomics = out->x_columns + out->insertions + 2 * out->deletions;
-    out->calls = ix->call_ncalls;
-    out->error = (uint32_t)(ix->call_add.error & 1);
-    out->overflow = (uint32_t)((ix->call_calls.error >> 1) & 1);
-    for (int i = 0; i < 3; ++i) out->step_ms[i] = ix->call_step_ms[i];
+    out->calls = ga.n_out;
+    out->error = (uint32_t)(ga.step[GenomeAcc::ADD].error & 1);
+    out->overflow = (uint32_t)((ga.step[GenomeAcc::OUT].error >> 1) & 1);
+    for (int i = 0; i < 3; ++i) out->step_ms[i] = ga.step_ms[i];
     return add_error_code(ix);
 }
 

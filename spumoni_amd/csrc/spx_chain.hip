@@ -60,10 +60,6 @@ __device__ inline unsigned long long group_maxu(unsigned long long v) {
     }
     return v;
 }
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
 
 struct Chained {  // the same in every lane of the group
     uint4 w0, w1, w2;

@@ -20,24 +20,21 @@
 //            start, seq and depth, the one that holds its last position writes end, and every thread the run passes
 //            through adds its mism to the record (zero sums are not added: an uncovered stretch costs nothing).
 //
+// The sequence table, the tiles, the head of a mapping with its checks and the host code that works on the index's
+// GenomeAcc are spx_genome_kernels.h's, shared by the coverage and the pileup.
+//
 // Control flow: every shuffle and ballot of k_cover_add_wave stands in a loop whose trip count is the same for the whole
 // wavefront (the list's length, the read's entries in steps of 64) or behind them; the other kernels shuffle and
 // synchronise only outside their loops.
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
-#include <cstring>
 #include <vector>
 
 #include "../../include/spumoni_cover.h"
-#include "spx_internal.h"
+#include "spx_genome_kernels.h"
 
 namespace spx {
 namespace {
 
-constexpr uint32_t OP_I = SPG_OP_I, OP_D = SPG_OP_D, OP_N = SPG_OP_N, OP_S = SPE_OP_S, OP_EQ = SPG_OP_EQ, OP_X = SPG_OP_X;
 constexpr uint32_t EMPTY = 0xffffffffu;
-constexpr int PER_THREAD = 16, TILE = 256 * PER_THREAD;  // positions of a finish / runs tile
 
 struct AddCounters {  // device; zeroed in front of every launch
     unsigned long long reads, mapped, added, skipped, intervals, atomics;
@@ -55,12 +52,6 @@ struct FinCounters {
 };
 constexpr int FIN_WORDS = sizeof(FinCounters) / 8;
 
-struct Table {
-    const uint64_t* P;  // n_seqs * strands + 1
-    uint64_t n_seqs;
-    uint32_t strands;
-    uint64_t G;
-};
 struct AddArgs {
     Table t;
     const uint4* map;       // 3 per read: spn_mapping
@@ -87,47 +78,16 @@ struct RunArgs {
     const uint32_t* mism;
     uint32_t min_depth;
     uint64_t cap, ntiles;
-    spd_run* runs;
+    spd_run* rec;
     uint64_t* tcnt;   // ntiles + 1: runs that start in a tile, then a 0
     uint64_t* toffs;  // ntiles + 1
     uint64_t* count;
     RunCounters* c;
 };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-__device__ inline unsigned long long wave_min(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long o = __shfl_xor(v, s);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ inline unsigned long long wave_max(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long o = __shfl_xor(v, s);
-        v = o > v ? o : v;
-    }
-    return v;
-}
+// the two halves of in_text
 __device__ inline bool covers(uint32_t op) { return op == OP_EQ || op == OP_X; }
 __device__ inline bool skips(uint32_t op) { return op == OP_D || op == OP_N; }
-__device__ inline bool is_op(uint32_t op) { return covers(op) || skips(op) || op == OP_I || op == OP_S; }
-__device__ inline uint64_t seq_start(const Table& t, uint64_t s) { return t.P[s * t.strands] / t.strands; }  // s <= n_seqs
-// the sequence that holds position x < G of the forward genome
-__device__ inline uint64_t seq_of(const Table& t, uint64_t x) {
-    uint64_t lo = 0, hi = t.n_seqs;  // F[lo] <= x < F[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (seq_start(t, mid) <= x)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 
 // A block's sums of reads[s] and indels[s]
 struct Tally {
@@ -158,51 +118,6 @@ __device__ inline void tally_flush(Tally& t, unsigned long long* counts) {
     if (t.indels[threadIdx.x]) atomicAdd(&counts[2 * (uint64_t)s + 1], t.indels[threadIdx.x]);
 }
 
-struct ReadHead {
-    uint32_t s;
-    uint64_t pos, span, i0, ne;  // pos: F[s] + target_start; span: target_end - target_start
-};
-// 0: unmapped, 1: the record and the offsets pass, 2: they do not
-__device__ inline int read_head(const AddArgs& a, uint64_t q, ReadHead& h) {
-    const uint4 w1 = a.map[3 * q + 1];
-    if (w1.x == SPN_UNMAPPED) return 0;
-    const uint4 w0 = a.map[3 * q];
-    const uint64_t ts = (uint64_t)w0.x | ((uint64_t)w0.y << 32), te = (uint64_t)w0.z | ((uint64_t)w0.w << 32);
-    const uint64_t i0 = a.ioffs[q], i1 = a.ioffs[q + 1];
-    if (w1.x >= a.t.n_seqs || i1 < i0 || i1 > a.in_entries || ts > te) return 2;
-    const uint64_t p0 = a.t.P[(uint64_t)w1.x * a.t.strands], p1 = a.t.P[(uint64_t)w1.x * a.t.strands + 1];
-    if (te > p1 - p0) return 2;
-    h.s = w1.x;
-    h.pos = p0 / a.t.strands + ts;
-    h.span = te - ts;
-    h.i0 = i0;
-    h.ne = i1 - i0;
-    return 1;
-}
-
-// Five sums leave a block as one set of atomics
-__device__ inline void block_counts(unsigned long long* part, unsigned long long* to, unsigned long long v0, unsigned long long v1,
-                                    unsigned long long v2, unsigned long long v3, unsigned long long v4) {
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    v2 = wave_sum(v2);
-    v3 = wave_sum(v3);
-    v4 = wave_sum(v4);
-    const uint32_t wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        part[wv * 5 + 0] = v0;
-        part[wv * 5 + 1] = v1;
-        part[wv * 5 + 2] = v2;
-        part[wv * 5 + 3] = v3;
-        part[wv * 5 + 4] = v4;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long v = part[threadIdx.x] + part[5 + threadIdx.x] + part[10 + threadIdx.x] + part[15 + threadIdx.x];
-        if (v) atomicAdd(to + threadIdx.x, v);
-    }
-}
-
 // A lane per read, a block over a stride of reads.
 __global__ __launch_bounds__(256) void k_cover_add_lane(AddArgs a) {
     __shared__ Tally tally;
@@ -210,8 +125,8 @@ __global__ __launch_bounds__(256) void k_cover_add_lane(AddArgs a) {
     tally_init(tally);
     unsigned long long mapped = 0, added = 0, skipped = 0, intervals = 0, columns = 0;
     for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < a.nreads; q += (uint64_t)gridDim.x * 256) {
-        ReadHead h;
-        const int st = read_head(a, q, h);
+        MapHead h;
+        const int st = map_head<false>(a, q, h);
         if (st == 0) continue;
         mapped += 1;
         if (st == 2) {
@@ -276,7 +191,8 @@ __global__ __launch_bounds__(256) void k_cover_add_lane(AddArgs a) {
     }
     tally_flush(tally, a.counts);
     if (skipped) atomicOr(&a.c->error, 1ull);
-    block_counts(part, &a.c->mapped, mapped, added, skipped, intervals, columns + 2 * intervals);
+    unsigned long long v[5] = {mapped, added, skipped, intervals, columns + 2 * intervals};
+    block_counts<5>(part, &a.c->mapped, v);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.c->reads = a.nreads;
 }
 
@@ -291,8 +207,8 @@ __global__ __launch_bounds__(256) void k_cover_add_wave(AddArgs a) {
     const unsigned long long below = (1ull << lane) - 1;
     unsigned long long added = 0, skipped = 0, intervals = 0, columns = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < nlong; i += (uint64_t)gridDim.x * 4) {
-        ReadHead h;
-        if (read_head(a, a.longs[i], h) != 1) continue;  // (the lane's kernel listed it because it is 1; the same for every lane)
+        MapHead h;
+        if (map_head<false>(a, a.longs[i], h) != 1) continue;  // (the lane's kernel listed it because it is 1; the same for every lane)
         const uint32_t* src = a.iops + h.i0;
         // pass 1: each lane over its entries, the sums behind the loop.  No 'S' between two others: the entries that
         // are not 'S' are as many as lie between the first and the last of them
@@ -358,7 +274,8 @@ __global__ __launch_bounds__(256) void k_cover_add_wave(AddArgs a) {
     }
     tally_flush(tally, a.counts);
     if (skipped) atomicOr(&a.c->error, 1ull);
-    block_counts(part, &a.c->added, added, skipped, intervals, columns + 2 * intervals, 0);
+    unsigned long long v[4] = {added, skipped, intervals, columns + 2 * intervals};
+    block_counts<4>(part, &a.c->added, v);
 }
 
 __global__ __launch_bounds__(256) void k_cover_summary_init(FinArgs a) {
@@ -391,8 +308,8 @@ __global__ __launch_bounds__(256) void k_cover_summary(FinArgs a) {
     l_cov[threadIdx.x] = l_max[threadIdx.x] = 0;
     l_bases[threadIdx.x] = l_mism[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t t0 = (uint64_t)blockIdx.x * TILE, t1 = t0 + TILE < a.t.G ? t0 + TILE : a.t.G;
-    const uint64_t p0 = t0 + (uint64_t)threadIdx.x * PER_THREAD, p1 = p0 + PER_THREAD < t1 ? p0 + PER_THREAD : t1;
+    const Tile x = tile_of(a.t.G);
+    const uint64_t t0 = x.t0, t1 = x.t1, p0 = x.p0, p1 = x.p1;
     if (p0 < t1) {
         uint64_t s = seq_of(a.t, p0), lo = seq_start(a.t, s), hi = seq_start(a.t, s + 1);
         Part acc{0, 0, 0, 0};
@@ -452,9 +369,8 @@ __device__ inline uint32_t count_starts(const RunArgs& a, uint64_t p0, uint64_t 
 __global__ __launch_bounds__(256) void k_cover_runs_count(RunArgs a) {
     using Reduce = hipcub::BlockReduce<uint32_t, 256>;
     __shared__ typename Reduce::TempStorage tmp;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TILE, t1 = t0 + TILE < a.t.G ? t0 + TILE : a.t.G;
-    const uint64_t p0 = t0 + (uint64_t)threadIdx.x * PER_THREAD, p1 = p0 + PER_THREAD < t1 ? p0 + PER_THREAD : t1;
-    const uint32_t n = Reduce(tmp).Sum(count_starts(a, p0, p1));
+    const Tile x = tile_of(a.t.G);
+    const uint32_t n = Reduce(tmp).Sum(count_starts(a, x.p0, x.p1));
     if (threadIdx.x == 0) {
         a.tcnt[blockIdx.x] = n;
         if (blockIdx.x == 0) a.tcnt[a.ntiles] = 0;
@@ -465,8 +381,8 @@ __global__ __launch_bounds__(256) void k_cover_runs_count(RunArgs a) {
 __global__ __launch_bounds__(256) void k_cover_runs_zero(RunArgs a) {
     const uint64_t total = a.toffs[a.ntiles], n = total < a.cap ? total : a.cap;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        a.runs[i].mismatches = 0;
-        a.runs[i].reserved = 0;
+        a.rec[i].mismatches = 0;
+        a.rec[i].reserved = 0;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *a.count = total;
@@ -478,8 +394,8 @@ __global__ __launch_bounds__(256) void k_cover_runs_zero(RunArgs a) {
 __global__ __launch_bounds__(256) void k_cover_runs_write(RunArgs a) {
     using Scan = hipcub::BlockScan<uint32_t, 256>;
     __shared__ typename Scan::TempStorage tmp;
-    const uint64_t t0 = (uint64_t)blockIdx.x * TILE, t1 = t0 + TILE < a.t.G ? t0 + TILE : a.t.G;
-    const uint64_t p0 = t0 + (uint64_t)threadIdx.x * PER_THREAD, p1 = p0 + PER_THREAD < t1 ? p0 + PER_THREAD : t1;
+    const Tile x = tile_of(a.t.G);
+    const uint64_t p0 = x.p0, p1 = x.p1;
     uint32_t before = 0;
     Scan(tmp).ExclusiveSum(count_starts(a, p0, p1), before);
     if (p0 >= p1) return;
@@ -505,9 +421,9 @@ __global__ __launch_bounds__(256) void k_cover_runs_write(RunArgs a) {
                 if (kept) {
                     cur = next++;
                     if (cur < a.cap) {
-                        a.runs[cur].start = p - lo;
-                        a.runs[cur].seq = (uint32_t)s;
-                        a.runs[cur].depth = d;
+                        a.rec[cur].start = p - lo;
+                        a.rec[cur].seq = (uint32_t)s;
+                        a.rec[cur].depth = d;
                     }
                 }
             } else {
@@ -518,143 +434,45 @@ __global__ __launch_bounds__(256) void k_cover_runs_write(RunArgs a) {
         sum += a.mism[p];
         ended = p + 1 == hi || a.depth[p + 1] != d;  // (p + 1 < hi <= G)
         if (ended && kept && cur < a.cap) {
-            a.runs[cur].end = p + 1 - lo;
-            if (sum) atomicAdd(&a.runs[cur].mismatches, sum);
+            a.rec[cur].end = p + 1 - lo;
+            if (sum) atomicAdd(&a.rec[cur].mismatches, sum);
         }
         prev = d;
     }
-    if (!ended && kept && cur < a.cap && sum) atomicAdd(&a.runs[cur].mismatches, sum);
+    if (!ended && kept && cur < a.cap && sum) atomicAdd(&a.rec[cur].mismatches, sum);
 }
 
-int need_table(const spx_index* ix, const char* who) {
-    if (!ix) {
-        set_error("index must be non-null");
-        return SPX_E_ARG;
-    }
-    if (!ix->map_P) {
-        set_error("%s needs the sequence table: the index has none (spn_set_sequences; spumoni build -s writes it)", who);
-        return SPX_E_ARG;
-    }
-    return SPX_OK;
-}
-Table table_of(const spx_index* ix) {
-    return Table{ix->map_P, ix->map_seq_lengths.size(), ix->map_strands, ix->n_text / ix->map_strands};
-}
-uint64_t tiles_of(uint64_t G) { return (G + TILE - 1) / TILE; }
+constexpr GenomeKind KIND = {"spd_cover_reset", "the coverage", "about 12 per base", "spd_cover_runs_begin", "spd_cover_runs_fetch", "out_runs",
+                             {ADD_WORDS, FIN_WORDS, RUN_WORDS}, 6, sizeof(spd_run)};
 
-void add_reset(spx_index* ix) {
-    product_reset(ix, ix->cover_add);
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->cover_acc, 0, sizeof ix->cover_acc);
-}
+int cover_add_enqueue(spx_index* ix, AddArgs& a, hipStream_t st) { return add_enqueue(ix, ix->cover, KIND, a, st, k_cover_add_lane, k_cover_add_wave); }
 
-// The list of one call and both kernels on st, between the step's two events.  Takes ix->mu.
-int add_enqueue(spx_index* ix, AddArgs& a, hipStream_t st) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    a.t = table_of(ix);
-    a.sw = (uint64_t)ix->cover_switch;
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->cover_scr[spx_index::D_LONG].reserve(a.nreads * 8 + 8, &p)) != SPX_OK) return rc;
-    a.longs = (uint64_t*)p;
-    return product_enqueue(ix->cover_add, ADD_WORDS, st, [&](void* counters) -> int {
-        a.c = (AddCounters*)counters;
-        if (!a.nreads) return SPX_OK;
-        const unsigned grid = (unsigned)std::min<uint64_t>((a.nreads + 255) / 256, 1024);
-        k_cover_add_lane<<<grid, 256, 0, st>>>(a);
-        SPX_HIP(hipGetLastError());
-        k_cover_add_wave<<<(unsigned)std::min<uint64_t>((a.nreads + 3) / 4, 2048), 256, 0, st>>>(a);
-        SPX_HIP(hipGetLastError());
-        return SPX_OK;
-    });
-}
-
-int finish_enqueue(spx_index* ix, FinArgs& a, const uint32_t* d_diff, uint32_t* d_depth, hipStream_t st) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    a.t = table_of(ix);
+int cover_finish_enqueue(spx_index* ix, FinArgs& a, const uint32_t* d_diff, uint32_t* d_depth, hipStream_t st) {
     a.depth = d_depth;
-    size_t cub_bytes = 0;
-    SPX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, cub_bytes, d_diff, d_depth, a.t.G, (hipStream_t) nullptr));
-    void* cub = nullptr;
-    int rc;
-    if ((rc = ix->cover_scr[spx_index::D_CUB].reserve(cub_bytes + 16, &cub)) != SPX_OK) return rc;
-    return product_enqueue(ix->cover_fin, FIN_WORDS, st, [&](void*) -> int {
-        SPX_HIP(hipcub::DeviceScan::InclusiveSum(cub, cub_bytes, d_diff, d_depth, a.t.G, st));
-        k_cover_summary_init<<<(unsigned)((a.t.n_seqs + 255) / 256), 256, 0, st>>>(a);
+    return finish_enqueue(ix, ix->cover, KIND, d_diff, d_depth, st, [&](const Table& t) -> int {
+        a.t = t;
+        k_cover_summary_init<<<(unsigned)((t.n_seqs + 255) / 256), 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
-        k_cover_summary<<<(unsigned)tiles_of(a.t.G), 256, 0, st>>>(a);
+        k_cover_summary<<<(unsigned)tiles_of(t.G), 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
         return SPX_OK;
     });
 }
 
-// count without write: the tiles' counts and their scan only; write without count: the second half of the host form,
-// which sizes its records from the count before it writes them
 int runs_enqueue(spx_index* ix, RunArgs& a, hipStream_t st, bool count, bool write) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    a.t = table_of(ix);
-    a.ntiles = tiles_of(a.t.G);
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->cover_scr[spx_index::D_TCNT].reserve((a.ntiles + 1) * 8, &p)) != SPX_OK) return rc;
-    a.tcnt = (uint64_t*)p;
-    if ((rc = ix->cover_scr[spx_index::D_TOFFS].reserve((a.ntiles + 1) * 8, &p)) != SPX_OK) return rc;
-    a.toffs = (uint64_t*)p;
-    size_t cub_bytes = 0;
-    SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, a.tcnt, a.toffs, a.ntiles + 1, (hipStream_t) nullptr));
-    void* cub = nullptr;
-    if ((rc = ix->cover_scr[spx_index::D_CUB2].reserve(cub_bytes + 16, &cub)) != SPX_OK) return rc;
-    auto launch = [&](void* counters) -> int {
-        a.c = (RunCounters*)counters;
-        if (count) {
-            k_cover_runs_count<<<(unsigned)a.ntiles, 256, 0, st>>>(a);
-            SPX_HIP(hipGetLastError());
-            SPX_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, a.tcnt, a.toffs, a.ntiles + 1, st));
-        }
-        if (write) {
+    return tiles_enqueue(
+        ix, ix->cover, KIND, a, st, count, write, [&] { k_cover_runs_count<<<(unsigned)a.ntiles, 256, 0, st>>>(a); },
+        [&]() -> int {
             k_cover_runs_zero<<<(unsigned)std::min<uint64_t>(a.cap / 256 + 1, 1024), 256, 0, st>>>(a);
             SPX_HIP(hipGetLastError());
             k_cover_runs_write<<<(unsigned)a.ntiles, 256, 0, st>>>(a);
             SPX_HIP(hipGetLastError());
-        }
-        return SPX_OK;
-    };
-    if (count) return product_enqueue(ix->cover_runs, RUN_WORDS, st, launch);
-    // the second half of the host form: the same counters, the step's end moved behind the write
-    if ((rc = launch(ix->cover_runs.counters.p)) != SPX_OK) return rc;
-    SPX_HIP(hipEventRecord(ix->cover_runs.ev1, st));
-    return SPX_OK;
-}
-
-// Waits for what a step enqueued last and takes its counters and its time.  Takes ix->mu.
-int step_collect(spx_index* ix, spx_index::Product& p, int words, int step) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventSynchronize(p.ev1));
-    unsigned long long c[ADD_WORDS] = {};
-    SPX_HIP(hipMemcpy(c, p.counters.p, (size_t)words * 8, hipMemcpyDeviceToHost));
-    SPX_HIP(hipEventElapsedTime(&ix->cover_step_ms[step], p.ev0, p.ev1));
-    if (step == 0)
-        for (int i = 0; i < 6; ++i) ix->cover_acc[i] += c[i];
-    if (step == 2) ix->cover_nruns = c[0];
-    p.error = step == 2 ? c[words - 1] : p.error | c[words - 1];
-    p.pending = false;
-    return SPX_OK;
-}
-
-int collect_all(spx_index* ix) {
-    int rc;
-    if (ix->cover_add.pending && (rc = step_collect(ix, ix->cover_add, ADD_WORDS, 0)) != SPX_OK) return rc;
-    if (ix->cover_fin.pending && (rc = step_collect(ix, ix->cover_fin, FIN_WORDS, 1)) != SPX_OK) return rc;
-    if (ix->cover_runs.pending && (rc = step_collect(ix, ix->cover_runs, RUN_WORDS, 2)) != SPX_OK) return rc;
-    return SPX_OK;
+            return SPX_OK;
+        });
 }
 
 int add_error_code(const spx_index* ix) {
-    if (ix->cover_add.error & 1) {
+    if (ix->cover.step[GenomeAcc::ADD].error & 1) {
         set_error("a read's mapping failed the coverage's checks (a sequence outside the table, a span outside the sequence, entries "
                   "whose text lengths disagree with it, an unknown operation, an 'S' between two other entries, or offsets outside "
                   "the entries): such a read adds nothing");
@@ -663,81 +481,27 @@ int add_error_code(const spx_index* ix) {
     return SPX_OK;
 }
 
-// The host forms' arrays are there and belong to the table in force.  The caller holds host_mu.
-int need_arrays(spx_index* ix, const char* who) {
-    int rc;
-    if ((rc = need_table(ix, who)) != SPX_OK) return rc;
-    if (ix->cover_dropped) {
-        set_error("%s: spn_set_sequences replaced the sequence table after spd_cover_reset and dropped the coverage: reset again", who);
-        return SPX_E_ARG;
-    }
-    if (!ix->cover_G) {
-        set_error("%s without a successful spd_cover_reset before it", who);
-        return SPX_E_ARG;
-    }
-    return SPX_OK;
-}
-
-// depth and the summary from the handle's arrays, when something was added since they were made.  The caller holds host_mu.
-int finish_host(spx_index* ix) {
-    if (!ix->cover_dirty) return SPX_OK;
-    hipStream_t st = nullptr;
-    int rc;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    FinArgs a{};
-    a.mism = (const uint32_t*)ix->cover_scr[spx_index::D_MISM].p;
-    a.counts = (const unsigned long long*)ix->cover_scr[spx_index::D_COUNTS].p;
-    a.out = (spd_seq_cover*)ix->cover_scr[spx_index::D_OUT].p;
-    if ((rc = finish_enqueue(ix, a, (const uint32_t*)ix->cover_scr[spx_index::D_DIFF].p, (uint32_t*)ix->cover_scr[spx_index::D_DEPTH].p, st)) !=
-        SPX_OK)
-        return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->cover_fin, FIN_WORDS, 1)) != SPX_OK) return rc;
-    ix->cover_dirty = false;
-    return SPX_OK;
-}
-
-// exactly `bytes`: the arrays of a genome are not given the scratch buffers' head-room
-int exact(spx_index::Scratch& sc, size_t bytes) {
-    if (sc.cap >= bytes) return SPX_OK;
-    if (sc.p) (void)hipFree(sc.p);
-    sc.p = nullptr;
-    sc.cap = 0;
-    SPX_HIP(hipMalloc(&sc.p, bytes));
-    sc.cap = bytes;
-    return SPX_OK;
-}
-
-void drop_arrays(spx_index* ix) {
-    for (int i : {spx_index::D_DIFF, spx_index::D_MISM, spx_index::D_DEPTH, spx_index::D_COUNTS, spx_index::D_OUT, spx_index::D_RUNS}) {
-        spx_index::Scratch& sc = ix->cover_scr[i];
-        if (sc.p) (void)hipFree(sc.p);
-        sc.p = nullptr;
-        sc.cap = 0;
-    }
-    ix->cover_G = 0;
-    ix->cover_runs_ready = false;
+template <typename T>
+T* array_of(spx_index* ix, int slot) {
+    return (T*)ix->cover.scr[slot].p;
 }
 
 }  // namespace
 
-void release_cover(spx_index* ix) {
-    for (auto& sc : ix->cover_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    product_release(ix->cover_add);
-    product_release(ix->cover_fin);
-    product_release(ix->cover_runs);
-}
+void release_cover(spx_index* ix) { release_acc(ix->cover); }
+int clone_cover(spx_index* src, spx_index* ix) { return src->cover.G ? spd_cover_reset(ix) : SPX_OK; }
+void cover_table_changed(spx_index* ix) { acc_table_changed(ix->cover); }
+int cover_need_arrays(spx_index* ix, const char* who) { return need_arrays(ix, ix->cover, KIND, who); }
 
-int clone_cover(spx_index* src, spx_index* ix) { return src->cover_G ? spd_cover_reset(ix) : SPX_OK; }
-
-void cover_table_changed(spx_index* ix) {
-    // (a kernel of an earlier call may still read the old table or the arrays)
-    for (spx_index::Product* p : {&ix->cover_add, &ix->cover_fin, &ix->cover_runs})
-        if (p->have && p->ev1) (void)hipEventSynchronize(p->ev1);  // (a reset sets `have` for the stats and creates no event)
-    if (!ix->cover_G) return;
-    drop_arrays(ix);
-    ix->cover_dropped = true;
+// depth and the summary from the handle's arrays, when something was added since they were made.  The caller holds host_mu.
+int cover_finish_host(spx_index* ix) {
+    return finish_host(ix, ix->cover, KIND, [&](hipStream_t st) {
+        FinArgs a{};
+        a.mism = array_of<const uint32_t>(ix, spx_index::D_MISM);
+        a.counts = array_of<const unsigned long long>(ix, spx_index::D_COUNTS);
+        a.out = array_of<spd_seq_cover>(ix, spx_index::D_OUT);
+        return cover_finish_enqueue(ix, a, array_of<const uint32_t>(ix, spx_index::D_DIFF), array_of<uint32_t>(ix, spx_index::D_DEPTH), st);
+    });
 }
 
 // What spd_cover_add_batch does behind its first check, for it and for spl_call_add_batch (spx_call.hip): `who` names the
@@ -749,7 +513,7 @@ int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32
     int rc;
     {
         std::lock_guard<std::mutex> hg(ix->host_mu);
-        if ((rc = need_arrays(ix, who)) != SPX_OK) return rc;
+        if ((rc = cover_need_arrays(ix, who)) != SPX_OK) return rc;
     }
     // the pipeline up to the mappings is spn_map_begin itself: its checks, its waits, its results on the device
     std::vector<spn_mapping> own;
@@ -769,7 +533,7 @@ int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32
         return SPX_E_ARG;
     }
     ix->map_ready = false;  // (the entries are this call's: nothing waits for spn_map_fetch)
-    if ((rc = need_arrays(ix, who)) != SPX_OK) return rc;
+    if ((rc = cover_need_arrays(ix, who)) != SPX_OK) return rc;
     if (nreads == 0) return SPX_OK;
     uint64_t mapped = 0;
     for (uint64_t q = 0; q < nreads; ++q) mapped += out_mappings[q].seq != SPN_UNMAPPED;
@@ -788,21 +552,18 @@ int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32
     a.iops = (const uint32_t*)ix->map_scr[spx_index::N_OPS].p;
     a.in_entries = n_in;
     a.nreads = nreads;
-    a.diff = (uint32_t*)ix->cover_scr[spx_index::D_DIFF].p;
-    a.mism = (uint32_t*)ix->cover_scr[spx_index::D_MISM].p;
-    a.counts = (unsigned long long*)ix->cover_scr[spx_index::D_COUNTS].p;
-    ix->cover_dirty = true;
-    ix->cover_runs_ready = false;
-    if ((rc = add_enqueue(ix, a, st)) != SPX_OK) return rc;
+    a.diff = array_of<uint32_t>(ix, spx_index::D_DIFF);
+    a.mism = array_of<uint32_t>(ix, spx_index::D_MISM);
+    a.counts = array_of<unsigned long long>(ix, spx_index::D_COUNTS);
+    ix->cover.dirty = true;
+    ix->cover.ready = false;
+    if ((rc = cover_add_enqueue(ix, a, st)) != SPX_OK) return rc;
     if (also && (rc = also(CoverBatch{d_maps, a.ioffs, a.iops, n_in, nreads, st})) != SPX_OK) return rc;
     if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->cover_add, ADD_WORDS, 0)) != SPX_OK) return rc;
+    if ((rc = step_collect(ix, ix->cover, KIND, GenomeAcc::ADD)) != SPX_OK) return rc;
     ix->cover_mapped += mapped;
     return add_error_code(ix);
 }
-
-int cover_need_arrays(spx_index* ix, const char* who) { return need_arrays(ix, who); }
-int cover_finish_host(spx_index* ix) { return finish_host(ix); }
 
 }  // namespace spx
 
@@ -824,7 +585,7 @@ int spd_cover_add_device(spx_index* ix, const spn_mapping* d_mappings, const uin
                   "and d_mism 4-byte aligned");
         return SPX_E_ARG;
     }
-    add_reset(ix);
+    add_reset(ix, ix->cover);
     AddArgs a{};
     a.map = (const uint4*)d_mappings;
     a.ioffs = d_op_offsets;
@@ -834,7 +595,7 @@ int spd_cover_add_device(spx_index* ix, const spn_mapping* d_mappings, const uin
     a.diff = d_diff;
     a.mism = d_mism;
     a.counts = (unsigned long long*)d_seq_counts;
-    return add_enqueue(ix, a, (hipStream_t)stream);
+    return cover_add_enqueue(ix, a, (hipStream_t)stream);
 }
 
 int spd_cover_finish_device(spx_index* ix, const uint32_t* d_diff, const uint32_t* d_mism, const uint64_t* d_seq_counts, uint32_t* d_depth,
@@ -853,7 +614,7 @@ int spd_cover_finish_device(spx_index* ix, const uint32_t* d_diff, const uint32_
     a.mism = d_mism;
     a.counts = (const unsigned long long*)d_seq_counts;
     a.out = d_out;
-    return finish_enqueue(ix, a, d_diff, d_depth, (hipStream_t)stream);
+    return cover_finish_enqueue(ix, a, d_diff, d_depth, (hipStream_t)stream);
 }
 
 int spd_cover_runs_device(spx_index* ix, const uint32_t* d_depth, const uint32_t* d_mism, uint32_t min_depth, uint64_t run_capacity,
@@ -873,7 +634,7 @@ int spd_cover_runs_device(spx_index* ix, const uint32_t* d_depth, const uint32_t
     a.mism = d_mism;
     a.min_depth = min_depth;
     a.cap = run_capacity;
-    a.runs = d_runs;
+    a.rec = d_runs;
     a.count = d_count;
     return runs_enqueue(ix, a, (hipStream_t)stream, true, true);
 }
@@ -884,37 +645,14 @@ int spd_cover_reset(spx_index* ix) {
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     const Table t = table_of(ix);
-    const size_t bytes[5] = {(size_t)(t.G + 1) * 4, (size_t)t.G * 4, (size_t)t.G * 4, (size_t)t.n_seqs * 16, (size_t)t.n_seqs * sizeof(spd_seq_cover)};
-    const int slot[5] = {spx_index::D_DIFF, spx_index::D_MISM, spx_index::D_DEPTH, spx_index::D_COUNTS, spx_index::D_OUT};
-    size_t need = 0;
-    for (int i = 0; i < 5; ++i)
-        if (ix->cover_scr[slot[i]].cap < bytes[i]) need += bytes[i];
-    size_t free_b = 0, total_b = 0;
-    SPX_HIP(hipMemGetInfo(&free_b, &total_b));
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if (need > free_b) {
-            set_error("spd_cover_reset: the coverage of %llu bases needs %llu more bytes of device memory (about 12 per base), %llu are free",
-                      (unsigned long long)t.G, (unsigned long long)need, (unsigned long long)free_b);
-            return SPX_E_UNSUPPORTED;
-        }
-        for (int i = 0; i < 5; ++i)
-            if ((rc = exact(ix->cover_scr[slot[i]], bytes[i])) != SPX_OK) {
-                drop_arrays(ix);
-                return rc;
-            }
-    }
-    hipStream_t st = nullptr;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    for (int i : {0, 1, 3}) SPX_HIP(hipMemsetAsync(ix->cover_scr[slot[i]].p, 0, bytes[i], st));
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    add_reset(ix);
-    ix->cover_G = t.G;
+    if ((rc = reset_arrays(ix, ix->cover, KIND, t.G,
+                           {{spx_index::D_DIFF, (size_t)(t.G + 1) * 4, true},
+                            {spx_index::D_MISM, (size_t)t.G * 4, true},
+                            {spx_index::D_DEPTH, (size_t)t.G * 4, false},
+                            {spx_index::D_COUNTS, (size_t)t.n_seqs * 16, true},
+                            {spx_index::D_OUT, (size_t)t.n_seqs * sizeof(spd_seq_cover), false}})) != SPX_OK)
+        return rc;
     ix->cover_mapped = 0;
-    ix->cover_dropped = false;
-    ix->cover_dirty = true;
-    ix->cover_runs_ready = false;
-    ix->cover_add.have = true;  // (the stats of no adds are zeros)
     return SPX_OK;
 }
 
@@ -934,15 +672,15 @@ int spd_cover_summary(spx_index* ix, spd_seq_cover* out, uint64_t n_seqs) {
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
     int rc;
-    if ((rc = need_arrays(ix, "spd_cover_summary")) != SPX_OK) return rc;
+    if ((rc = cover_need_arrays(ix, "spd_cover_summary")) != SPX_OK) return rc;
     if (n_seqs != ix->map_seq_lengths.size()) {
         set_error("spd_cover_summary: n_seqs is %llu, the sequence table has %llu", (unsigned long long)n_seqs,
                   (unsigned long long)ix->map_seq_lengths.size());
         return SPX_E_ARG;
     }
     SPX_HIP(hipSetDevice(ix->device));
-    if ((rc = finish_host(ix)) != SPX_OK) return rc;
-    SPX_HIP(hipMemcpy(out, ix->cover_scr[spx_index::D_OUT].p, n_seqs * sizeof(spd_seq_cover), hipMemcpyDeviceToHost));
+    if ((rc = cover_finish_host(ix)) != SPX_OK) return rc;
+    SPX_HIP(hipMemcpy(out, ix->cover.scr[spx_index::D_OUT].p, n_seqs * sizeof(spd_seq_cover), hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -954,57 +692,16 @@ int spd_cover_runs_begin(spx_index* ix, uint32_t min_depth, uint64_t* n_runs) {
     *n_runs = 0;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     int rc;
-    if ((rc = need_arrays(ix, "spd_cover_runs_begin")) != SPX_OK) return rc;
-    SPX_HIP(hipSetDevice(ix->device));
-    ix->cover_runs_ready = false;
-    if ((rc = finish_host(ix)) != SPX_OK) return rc;
-    hipStream_t st = nullptr;
-    if ((rc = ctx_stream_of(ix, &st)) != SPX_OK) return rc;
-    void* d_n = nullptr;
-    if ((rc = ix->cover_scr[spx_index::D_NRUNS].reserve(8, &d_n)) != SPX_OK) return rc;
+    if ((rc = cover_need_arrays(ix, "spd_cover_runs_begin")) != SPX_OK) return rc;
     RunArgs a{};
-    a.depth = (const uint32_t*)ix->cover_scr[spx_index::D_DEPTH].p;
-    a.mism = (const uint32_t*)ix->cover_scr[spx_index::D_MISM].p;
+    a.depth = array_of<const uint32_t>(ix, spx_index::D_DEPTH);
+    a.mism = array_of<const uint32_t>(ix, spx_index::D_MISM);
     a.min_depth = min_depth;
-    a.count = (uint64_t*)d_n;
-    // count, the one wait of the runs' own, the records at their exact size, write
-    if ((rc = runs_enqueue(ix, a, st, true, false)) != SPX_OK) return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    uint64_t total = 0;
-    SPX_HIP(hipMemcpy(&total, a.toffs + a.ntiles, 8, hipMemcpyDeviceToHost));
-    void* d_runs = nullptr;
-    if ((rc = ix->cover_scr[spx_index::D_RUNS].reserve(total * sizeof(spd_run) + 32, &d_runs)) != SPX_OK) return rc;
-    a.runs = (spd_run*)d_runs;
-    a.cap = total;
-    if ((rc = runs_enqueue(ix, a, st, false, true)) != SPX_OK) return rc;
-    if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = step_collect(ix, ix->cover_runs, RUN_WORDS, 2)) != SPX_OK) return rc;
-    ix->cover_runs_ready = true;
-    ix->cover_runs_ready_n = total;
-    *n_runs = total;
-    return SPX_OK;
+    return records_begin(ix, ix->cover, KIND, a, n_runs, [&] { return cover_finish_host(ix); },
+                         [&](RunArgs& r, hipStream_t st, bool count, bool write) { return runs_enqueue(ix, r, st, count, write); });
 }
 
-int spd_cover_runs_fetch(spx_index* ix, spd_run* out_runs) {
-    if (!ix) {
-        set_error("index must be non-null");
-        return SPX_E_ARG;
-    }
-    std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (!ix->cover_runs_ready) {
-        set_error("spd_cover_runs_fetch without a successful spd_cover_runs_begin before it");
-        return SPX_E_ARG;
-    }
-    if (ix->cover_runs_ready_n && !out_runs) {
-        set_error("out_runs must be non-null");
-        return SPX_E_ARG;
-    }
-    ix->cover_runs_ready = false;
-    if (!ix->cover_runs_ready_n) return SPX_OK;
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipMemcpy(out_runs, ix->cover_scr[spx_index::D_RUNS].p, ix->cover_runs_ready_n * sizeof(spd_run), hipMemcpyDeviceToHost));
-    return SPX_OK;
-}
+int spd_cover_runs_fetch(spx_index* ix, spd_run* out_runs) { return records_fetch(ix, &spx_index::cover, KIND, out_runs); }
 
 int spd_cover_depth(spx_index* ix, uint64_t first, uint64_t count, uint32_t* out_depth, uint32_t* out_mism) {
     if (!ix) {
@@ -1013,19 +710,13 @@ int spd_cover_depth(spx_index* ix, uint64_t first, uint64_t count, uint32_t* out
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
     int rc;
-    if ((rc = need_arrays(ix, "spd_cover_depth")) != SPX_OK) return rc;
-    if (first > ix->cover_G || count > ix->cover_G - first) {
-        set_error("spd_cover_depth: [%llu, %llu + %llu) does not lie in the forward genome of %llu bases", (unsigned long long)first,
-                  (unsigned long long)first, (unsigned long long)count, (unsigned long long)ix->cover_G);
-        return SPX_E_ARG;
-    }
+    if ((rc = cover_need_arrays(ix, "spd_cover_depth")) != SPX_OK) return rc;
+    if ((rc = check_range(ix->cover, "spd_cover_depth", first, count)) != SPX_OK) return rc;
     SPX_HIP(hipSetDevice(ix->device));
-    if ((rc = finish_host(ix)) != SPX_OK) return rc;
+    if ((rc = cover_finish_host(ix)) != SPX_OK) return rc;
     if (!count) return SPX_OK;
-    if (out_depth)
-        SPX_HIP(hipMemcpy(out_depth, (const uint32_t*)ix->cover_scr[spx_index::D_DEPTH].p + first, count * 4, hipMemcpyDeviceToHost));
-    if (out_mism)
-        SPX_HIP(hipMemcpy(out_mism, (const uint32_t*)ix->cover_scr[spx_index::D_MISM].p + first, count * 4, hipMemcpyDeviceToHost));
+    if (out_depth) SPX_HIP(hipMemcpy(out_depth, array_of<const uint32_t>(ix, spx_index::D_DEPTH) + first, count * 4, hipMemcpyDeviceToHost));
+    if (out_mism) SPX_HIP(hipMemcpy(out_mism, array_of<const uint32_t>(ix, spx_index::D_MISM) + first, count * 4, hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -1034,22 +725,23 @@ int spd_last_cover_stats(spx_index* ix, spd_cover_stats* out) {
         set_error("null argument");
         return SPX_E_ARG;
     }
-    if (!ix->cover_add.have && !ix->cover_fin.have && !ix->cover_runs.have) {
+    if (!have_any(ix->cover)) {
         set_error("no coverage has been computed on this index yet");
         return SPX_E_ARG;
     }
-    const int rc = collect_all(ix);
+    const int rc = collect_all(ix, ix->cover, KIND);
     if (rc != SPX_OK) return rc;
-    out->reads = ix->cover_acc[0];
-    out->mapped = ix->cover_acc[1];
-    out->added = ix->cover_acc[2];
-    out->skipped = ix->cover_acc[3];
-    out->intervals = ix->cover_acc[4];
-    out->atomics = ix->cover_acc[5];
-    out->runs = ix->cover_nruns;
-    out->error = (uint32_t)(ix->cover_add.error & 1);
-    out->overflow = (uint32_t)((ix->cover_runs.error >> 1) & 1);
-    for (int i = 0; i < 3; ++i) out->step_ms[i] = ix->cover_step_ms[i];
+    const GenomeAcc& ga = ix->cover;
+    out->reads = ga.acc[0];
+    out->mapped = ga.acc[1];
+    out->added = ga.acc[2];
+    out->skipped = ga.acc[3];
+    out->intervals = ga.acc[4];
+    out->atomics = ga.acc[5];
+    out->runs = ga.n_out;
+    out->error = (uint32_t)(ga.step[GenomeAcc::ADD].error & 1);
+    out->overflow = (uint32_t)((ga.step[GenomeAcc::OUT].error >> 1) & 1);
+    for (int i = 0; i < 3; ++i) out->step_ms[i] = ga.step_ms[i];
     out->kernel_ms = out->step_ms[0] + out->step_ms[1] + out->step_ms[2];
     return add_error_code(ix);
 }

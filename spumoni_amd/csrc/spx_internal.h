@@ -160,6 +160,11 @@ struct BatchArgs {
     uint64_t len_mask_pairs;  // 16-byte pairs len_mask holds (sized from total_chars: checked, the caller may be wrong)
 };
 
+__device__ inline unsigned long long wave_sum(unsigned long long v) {  // over the wavefront's 64 lanes, in every lane
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
 }  // namespace spx
 
 struct spc_params;  // include/spumoni_chain.h
@@ -363,35 +368,31 @@ struct spx_index {
     uint64_t map_acc[8] = {};
     bool map_ready = false;
     uint64_t map_ready_n = 0, map_ready_reads = 0;
-    // coverage (spx_cover.hip): one Product per step -- add, finish, runs --, so that each keeps its counters and its
-    // events; the list of the reads that take a wavefront, the scans' space, the runs' tile counts and offsets (under
-    // mu); then the host forms' arrays -- diff, mism, depth, the per-sequence counts --, the summary, the runs and their
-    // count (under host_mu).  cover_G: the forward genome the arrays were sized for, 0 without a reset; cover_dropped:
-    // spn_set_sequences took them away; cover_mapped: mapped reads added since the reset; cover_dirty: depth is older
-    // than diff.  cover_acc: reads, mapped, added, skipped, intervals, atomics of the adds the stats speak of
-    enum { D_LONG, D_CUB, D_CUB2, D_TCNT, D_TOFFS, D_DIFF, D_MISM, D_DEPTH, D_COUNTS, D_OUT, D_RUNS, D_NRUNS, D_COUNT };
-    Scratch cover_scr[D_COUNT];
-    Product cover_add, cover_fin, cover_runs;  // (acc unused: cover_acc)
-    uint64_t cover_G = 0, cover_mapped = 0, cover_acc[6] = {}, cover_nruns = 0;
-    bool cover_dropped = false, cover_dirty = false, cover_runs_ready = false;
-    uint64_t cover_runs_ready_n = 0;
-    int cover_switch = 64;  // "cover_switch" option: a read of more entries than this takes a wavefront
-    float cover_step_ms[3] = {};
-    // pileup and calls (spx_call.hip): one Product per step -- add, finish, calls -- as the coverage has; the list of the
-    // reads that take a wavefront, the scans' space, the calls' tile counts and offsets (under mu); then the host forms'
-    // arrays -- alt, other, ins, ddiff, del --, the batch's reads and their offsets, the calls and their count (under
-    // host_mu).  call_G, call_dropped, call_dirty: as the coverage's, for del and ddiff.  call_acc: reads, mapped, added,
-    // skipped, X columns, other columns, 'I' entries, 'D' entries of the adds the stats speak of.  The reads are copied
-    // on a stream of the product's own, so that the copy overlaps spn_map_begin
-    enum { PL_LONG, PL_CUB, PL_CUB2, PL_TCNT, PL_TOFFS, PL_ALT, PL_OTHER, PL_INS, PL_DDIFF, PL_DEL, PL_READS, PL_ROFFS, PL_CALLS,
-           PL_NCALLS, PL_COUNT };
-    Scratch call_scr[PL_COUNT];
-    Product call_add, call_fin, call_calls;  // (acc unused: call_acc)
-    uint64_t call_G = 0, call_acc[8] = {}, call_ncalls = 0;
-    bool call_dropped = false, call_dirty = false, call_ready = false;
-    uint64_t call_ready_n = 0;
-    int call_switch = 64;  // "call_switch" option: a read of more entries than this takes a wavefront
-    float call_step_ms[3] = {};
+    // What the coverage and the pileup keep alike (spx_genome_kernels.h): one Product per step -- add, finish, output --; the
+    // shared scratch: the list of the reads that take a wavefront, the scans' space, the output's tile counts and offsets
+    // (under mu), its count word and records (under host_mu); from S_OWN on the product's own, first the ARRAYS arrays a
+    // reset sizes for the genome.  G: the forward genome they were sized for, 0 without a reset; dropped: spn_set_sequences
+    // took them away; dirty: the finished arrays are older than the summed ones; acc: the add's first counters over the adds
+    // the stats speak of; n_out: what the last output counted; ready, ready_n: the records that wait for the fetch
+    struct GenomeAcc {
+        enum { ADD, FIN, OUT };
+        enum { S_LONG, S_CUB, S_CUB2, S_TCNT, S_TOFFS, S_NOUT, S_RECORDS, S_OWN, ARRAYS = 5, S_COUNT = S_OWN + 7 };
+        Product step[3];  // (acc unused)
+        Scratch scr[S_COUNT];
+        uint64_t G = 0, acc[8] = {}, n_out = 0, ready_n = 0;
+        bool dropped = false, dirty = false, ready = false;
+        int sw = 64;  // a read of more entries than this takes a wavefront
+        float step_ms[3] = {};
+    };
+    // coverage (spx_cover.hip): diff, mism, depth, the per-sequence counts, the summary; the output is the runs.  acc: reads,
+    // mapped, added, skipped, intervals, atomics.  sw: the "cover_switch" option.  cover_mapped: mapped reads since the reset
+    enum { D_DIFF = GenomeAcc::S_OWN, D_MISM, D_DEPTH, D_COUNTS, D_OUT };
+    GenomeAcc cover;
+    uint64_t cover_mapped = 0;
+    // pileup and calls (spx_call.hip): alt, other, ins, ddiff, del, the batch's reads and their offsets (copied on a stream of
+    // the product's own, so that the copy overlaps spn_map_begin); the output is the calls.  sw: the "call_switch" option
+    enum { PL_ALT = GenomeAcc::S_OWN, PL_OTHER, PL_INS, PL_DDIFF, PL_DEL, PL_READS, PL_ROFFS };
+    GenomeAcc call;
     hipStream_t call_copy_s = nullptr;
     hipEvent_t call_copy_ev = nullptr;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
@@ -534,15 +535,14 @@ void release_extend(spx_index* ix);
 // spx_map.hip: the same for the mappings and the sequence table; and the table of `src` copied into a fresh clone
 void release_map(spx_index* ix);
 int clone_map(spx_index* src, spx_index* ix);
-// spx_cover.hip: the same for the coverage; and what spn_set_sequences does to it (the caller holds host_mu and mu): the
-// host forms' arrays were sized for the table that goes
+int need_table(const spx_index* ix, const char* who);  // SPX_E_ARG and a message naming `who` unless ix has a sequence table
+// spx_cover.hip: the same for the coverage; what spn_set_sequences does to it (the caller holds host_mu and mu): the host
+// forms' arrays were sized for the table that goes; and a fresh clone of an index that has the arrays gets its own, empty
 void release_cover(spx_index* ix);
 void cover_table_changed(spx_index* ix);
-// ... and a fresh clone of an index that has the arrays gets its own, empty
 int clone_cover(spx_index* src, spx_index* ix);
 // ... and what spd_cover_add_batch does behind its first check, for it and for spl_call_add_batch: `also` (may be empty)
-// enqueues the caller's own work on the records and entries of the batch, behind the coverage's add and in front of the
-// one wait; the host forms' arrays checked (the caller holds host_mu) and depth brought up to date
+// enqueues the caller's work on the batch's records and entries, behind the coverage's add and in front of the one wait
 struct CoverBatch {
     const spn_mapping* d_mappings;
     const uint64_t* d_op_offsets;
@@ -554,8 +554,8 @@ int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32
                          uint64_t nreads, uint64_t min_length, int want_docs, const struct ::spc_params* chain_params,
                          const struct ::spa_params* align_params, const struct ::spe_params* extend_params, spn_mapping* out_mappings,
                          const std::function<int(const CoverBatch&)>& also);
-int cover_need_arrays(spx_index* ix, const char* who);
-int cover_finish_host(spx_index* ix);
+int cover_need_arrays(spx_index* ix, const char* who);  // the host forms' arrays are there (the caller holds host_mu)
+int cover_finish_host(spx_index* ix);                   // ... and depth is brought up to date
 // spx_call.hip: the same three for the pileup and the calls
 void release_call(spx_index* ix);
 void call_table_changed(spx_index* ix);

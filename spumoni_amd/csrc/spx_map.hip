@@ -58,10 +58,6 @@ struct MapArgs {
     MapCounters* c;
 };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
 __device__ inline void write_unmapped(const MapArgs& a, uint64_t q) {
     a.out[3 * q] = make_uint4(0, 0, 0, 0);
     a.out[3 * q + 1] = make_uint4(SPN_UNMAPPED, 0, 0, 0);
@@ -304,18 +300,6 @@ __global__ __launch_bounds__(256) void k_map_write(MapArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.c->reads = a.nreads;
 }
 
-int need_table(const spx_index* ix, const char* who) {
-    if (!ix) {
-        set_error("index must be non-null");
-        return SPX_E_ARG;
-    }
-    if (!ix->map_P) {
-        set_error("%s needs the sequence table: the index has none (spn_set_sequences; spumoni build -s writes it)", who);
-        return SPX_E_ARG;
-    }
-    return SPX_OK;
-}
-
 void map_reset(spx_index* ix) {
     product_reset(ix, ix->map);
     std::lock_guard<std::mutex> g(ix->mu);
@@ -392,6 +376,18 @@ int map_error_code(const spx_index* ix) {
 }
 
 }  // namespace
+
+int need_table(const spx_index* ix, const char* who) {
+    if (!ix) {
+        set_error("index must be non-null");
+        return SPX_E_ARG;
+    }
+    if (!ix->map_P) {
+        set_error("%s needs the sequence table: the index has none (spn_set_sequences; spumoni build -s writes it)", who);
+        return SPX_E_ARG;
+    }
+    return SPX_OK;
+}
 
 void release_map(spx_index* ix) {
     if (ix->map_P) (void)hipFree(ix->map_P);

@@ -91,10 +91,6 @@ __device__ inline unsigned long long group_maxu(unsigned long long v) {
     }
     return v;
 }
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
 
 struct Side {
     uint32_t len, equal;  // steps of the extension, equal characters inside
