@@ -163,37 +163,18 @@ __global__ __launch_bounds__(64) void k_fill_wave(AlignArgs a) {
 int align_reserve(spx_index* ix, AlignArgs& a, bool own_goffs, bool own_gaps, size_t* cub_bytes, void** cub) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    void* p = nullptr;
-    int rc;
-    if ((rc = ix->align_scr[spx_index::L_CNT].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
-    a.cnt = (uint64_t*)p;
-    if (own_goffs) {
-        if ((rc = ix->align_scr[spx_index::L_GOFFS].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
-        a.goffs = (uint64_t*)p;
-    }
-    if (own_gaps) {
-        if ((rc = ix->align_scr[spx_index::L_GAPS].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
-        a.gaps = (uint4*)p;
-    }
-    if ((rc = ix->align_scr[spx_index::L_DESC].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
-    a.desc = (ulonglong2*)p;
-    if ((rc = ix->align_scr[spx_index::L_LIST].reserve(a.cap * 4 + 16, &p)) != SPX_OK) return rc;
-    a.list = (uint32_t*)p;
-    *cub_bytes = 0;
-    SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, *cub_bytes, a.cnt, a.goffs, a.nreads + 1, (hipStream_t) nullptr));
-    if ((rc = ix->align_scr[spx_index::L_CUB].reserve(*cub_bytes + 16, cub)) != SPX_OK) return rc;
-    return SPX_OK;
+    return reserve_gaps(ix->align_scr, a, own_goffs, own_gaps, 0, cub_bytes, cub);
 }
 
-// The align kernels on st, between the index's two events, with an event between the steps.  Takes ix->mu.
+// The align kernels on st, between the index's two events, with a mark where each of the four steps begins (none for a
+// batch without reads: its step times are zeros).  Takes ix->mu.
 int align_enqueue(spx_index* ix, AlignArgs& a, size_t cub_bytes, void* cub, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    for (auto& e : ix->ev_align)
-        if (!e) SPX_HIP(hipEventCreate(&e));
-    ix->align_steps = false;
-    return product_enqueue(ix->align, ALIGN_WORDS, st, [&](void* counters) -> int {
+    spx_index::Product& p = ix->align;
+    return product_enqueue(p, ALIGN_WORDS, st, [&](void* counters) -> int {
         a.c = (AlignCounters*)counters;
+        int rc;
         if (!a.nreads) {
             SPX_HIP(hipMemsetAsync(a.goffs, 0, 8, st));
             return SPX_OK;
@@ -202,10 +183,10 @@ int align_enqueue(spx_index* ix, AlignArgs& a, size_t cub_bytes, void* cub, hipS
         k_align_count<<<read_grid, 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
         SPX_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, a.cnt, a.goffs, a.nreads + 1, st));
-        SPX_HIP(hipEventRecord(ix->ev_align[0], st));
+        if ((rc = product_mark(p, 1, st)) != SPX_OK) return rc;
         k_align_walk<<<read_grid, 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
-        SPX_HIP(hipEventRecord(ix->ev_align[1], st));
+        if ((rc = product_mark(p, 2, st)) != SPX_OK) return rc;
         if (a.cap) {
             // (the number of gaps is the device's: the grid covers the capacity, and lanes past the total leave at once)
             k_fill_small<<<(unsigned)((a.cap + 255) / 256), 256, 0, st>>>(a);
@@ -213,24 +194,11 @@ int align_enqueue(spx_index* ix, AlignArgs& a, size_t cub_bytes, void* cub, hipS
             k_fill_wave<<<(unsigned)std::min<uint64_t>(a.cap, 4096), 64, 0, st>>>(a);
             SPX_HIP(hipGetLastError());
         }
-        SPX_HIP(hipEventRecord(ix->ev_align[2], st));
+        if ((rc = product_mark(p, 3, st)) != SPX_OK) return rc;
         k_align_reduce<<<std::min(read_grid, 1024u), 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
-        ix->align_steps = true;
         return SPX_OK;
-    });
-}
-int align_collect(spx_index* ix) {
-    const bool steps = ix->align_steps;
-    int rc = product_collect(ix, ix->align, ALIGN_WORDS, 5);
-    if (rc != SPX_OK) return rc;
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->align_step_ms, 0, sizeof ix->align_step_ms);
-    if (steps) {
-        hipEvent_t e[5] = {ix->align.ev0, ix->ev_align[0], ix->ev_align[1], ix->ev_align[2], ix->align.ev1};
-        for (int i = 0; i < 4; ++i) SPX_HIP(hipEventElapsedTime(&ix->align_step_ms[i], e[i], e[i + 1]));
-    }
-    return SPX_OK;
+    }, a.nreads ? 0 : -1);
 }
 int align_error_code(const spx_index* ix) {
     if (ix->align.error & 1) {
@@ -243,13 +211,7 @@ int align_error_code(const spx_index* ix) {
 
 }  // namespace
 
-void release_align(spx_index* ix) {
-    for (auto& sc : ix->align_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    for (auto& e : ix->ev_align)
-        if (e) (void)hipEventDestroy(e);
-    product_release(ix->align);
-}
+void release_align(spx_index* ix) { release(ix->align_scr, spx_index::L_COUNT, &ix->align); }
 
 }  // namespace spx
 
@@ -314,7 +276,7 @@ int spa_last_align_stats(spx_index* ix, spa_align_stats* out) {
         return SPX_E_ARG;
     }
     if (ix->align.pending) {
-        const int rc = align_collect(ix);
+        const int rc = product_collect(ix, ix->align, ALIGN_WORDS, 5);
         if (rc != SPX_OK) return rc;
     }
     out->reads = ix->align.acc[0];
@@ -325,7 +287,7 @@ int spa_last_align_stats(spx_index* ix, spa_align_stats* out) {
     out->error = (uint32_t)(ix->align.error & 1);
     out->overflow = (uint32_t)((ix->align.error >> 1) & 1);
     out->kernel_ms = ix->align.ms;
-    for (int i = 0; i < 4; ++i) out->step_ms[i] = ix->align_step_ms[i];
+    for (int i = 0; i < 4; ++i) out->step_ms[i] = ix->align.step_ms[i];
     return align_error_code(ix);
 }
 
@@ -334,7 +296,6 @@ int spa_last_align_stats(spx_index* ix, spa_align_stats* out) {
 int spa_align_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
                     uint64_t nreads, uint64_t min_length, int want_docs, const spc_params* chain_params,
                     const spa_params* align_params, spa_alignment* out_alignments, spc_chain* out_chains, uint64_t* out_values) {
-    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
     if (spx_device_count() <= 0) {
         set_error("no HIP device visible: the alignments are computed on the GPU and there is no CPU fallback");
         return SPX_E_NODEVICE;
@@ -342,37 +303,16 @@ int spa_align_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
     int rc = check_align_params(ix, align_params);
     if (rc != SPX_OK) return rc;
     if ((rc = chain_check_params(ix, chain_params)) != SPX_OK) return rc;
-    if (min_length == 0) {
-        set_error("min_length must be at least 1: a position of length 0 matches nothing");
-        return SPX_E_ARG;
-    }
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
-    if (!ix->has_samples || !ix->text) {
-        set_error("the alignments need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)");
-        return SPX_E_ARG;
-    }
-    if (want_docs && !ix->has_docs) {
-        set_error("document ids requested but the index has no document array");
-        return SPX_E_ARG;
-    }
-    if (nreads && (!seqs || !offsets || !out_alignments)) {
-        set_error("seqs, offsets and out_alignments must be non-null");
-        return SPX_E_ARG;
-    }
-    if (nreads > PIECE_READS || (nreads && offsets[nreads] >= offsets[0] && offsets[nreads] - offsets[0] > PIECE_CHARS)) {
-        set_error("one piece per call: at most 32 Mi characters and 4 Mi reads");
-        return SPX_E_ARG;
-    }
+    if ((rc = check_batch(ix, "the alignments", BATCH_MIN_LENGTH | BATCH_TEXT | BATCH_ONE_PIECE, min_length, digest_kind, want_docs,
+                          nreads && (!seqs || !offsets || !out_alignments) ? "seqs, offsets and out_alignments must be non-null" : nullptr,
+                          offsets, nreads)) != SPX_OK)
+        return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     product_reset(ix, ix->align);
     product_reset(ix, ix->chain);
     if (nreads == 0) {
         ix->align.have = ix->chain.have = true;  // (the stats of an empty batch are zeros)
-        std::memset(ix->align_step_ms, 0, sizeof ix->align_step_ms);
         return SPX_OK;
     }
     // what is sized by the reads, before anything is enqueued; what is sized by the matches when their number is known
@@ -413,11 +353,10 @@ int spa_align_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
                 SPX_HIP(hipMemcpyAsync(out_chains, d_chains, m.nreads * sizeof(spc_chain), hipMemcpyDeviceToHost, m.stream));
             return SPX_OK;
         });
-    ix->mems_ready = false;  // (the records were this call's: nothing waits for spm_mems_fetch)
     if (rc != SPX_OK) return rc;
     spc_chain_stats cs;
     if ((rc = spc_last_chain_stats(ix, &cs)) != SPX_OK) return rc;
-    if ((rc = align_collect(ix)) != SPX_OK) return rc;
+    if ((rc = product_collect(ix, ix->align, ALIGN_WORDS, 5)) != SPX_OK) return rc;
     return align_error_code(ix);
 }
 

@@ -225,5 +225,35 @@ int check_align_params(const spx_index* ix, const spa_params* p) {
     return SPX_OK;
 }
 
+// The six scratch slots the alignments and both CIGARs have alike, reserved before any kernel is enqueued (a buffer that
+// grows is freed first: a device-wide wait): the gap counts, their offsets and the per-gap table unless they are the
+// caller's arrays, where each gap's strings start, the list of the gaps that take a wavefront, and the scans' space -- for
+// the scan of the counts and `other_scans` bytes at least.  The caller holds ix->mu and has set the device.
+static_assert(spx_index::TB_CNT == spx_index::L_CNT && spx_index::TB_GOFFS == spx_index::L_GOFFS && spx_index::TB_GAPS == spx_index::L_GAPS &&
+                  spx_index::TB_DESC == spx_index::L_DESC && spx_index::TB_LIST == spx_index::L_LIST && spx_index::TB_CUB == spx_index::L_CUB,
+              "reserve_gaps fills the slots of either product");
+int reserve_gaps(spx_index::Scratch* scr, AlignArgs& a, bool own_goffs, bool own_gaps, size_t other_scans, size_t* cub_bytes, void** cub) {
+    void* p = nullptr;
+    int rc;
+    if ((rc = scr[spx_index::L_CNT].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
+    a.cnt = (uint64_t*)p;
+    if (own_goffs) {
+        if ((rc = scr[spx_index::L_GOFFS].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
+        a.goffs = (uint64_t*)p;
+    }
+    if (own_gaps) {
+        if ((rc = scr[spx_index::L_GAPS].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
+        a.gaps = (uint4*)p;
+    }
+    if ((rc = scr[spx_index::L_DESC].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
+    a.desc = (ulonglong2*)p;
+    if ((rc = scr[spx_index::L_LIST].reserve(a.cap * 4 + 16, &p)) != SPX_OK) return rc;
+    a.list = (uint32_t*)p;
+    *cub_bytes = 0;
+    SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, *cub_bytes, a.cnt, a.goffs, a.nreads + 1, (hipStream_t) nullptr));
+    *cub_bytes = std::max(*cub_bytes, other_scans);
+    return scr[spx_index::L_CUB].reserve(*cub_bytes + 16, cub);
+}
+
 }  // namespace
 }  // namespace spx

@@ -284,11 +284,7 @@ int chain_check_params(const spx_index* ix, const spc_params* p) {
     }
     return SPX_OK;
 }
-void release_chain(spx_index* ix) {
-    for (auto& sc : ix->chain_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    product_release(ix->chain);
-}
+void release_chain(spx_index* ix) { release(ix->chain_scr, spx_index::H_COUNT, &ix->chain); }
 
 }  // namespace spx
 
@@ -351,37 +347,16 @@ int spc_last_chain_stats(spx_index* ix, spc_chain_stats* out) {
 int spc_chain_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,
                     uint64_t nreads, uint64_t min_length, int want_docs, const spc_params* params, spc_chain* out_chains,
                     uint64_t* out_values) {
-    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
     if (spx_device_count() <= 0) {
         set_error("no HIP device visible: the chains are computed on the GPU and there is no CPU fallback");
         return SPX_E_NODEVICE;
     }
     int rc = chain_check_params(ix, params);
     if (rc != SPX_OK) return rc;
-    if (min_length == 0) {
-        set_error("min_length must be at least 1: a position of length 0 matches nothing");
-        return SPX_E_ARG;
-    }
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
-    if (!ix->has_samples || !ix->text) {
-        set_error("the chains need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)");
-        return SPX_E_ARG;
-    }
-    if (want_docs && !ix->has_docs) {
-        set_error("document ids requested but the index has no document array");
-        return SPX_E_ARG;
-    }
-    if (nreads && (!seqs || !offsets || !out_chains)) {
-        set_error("seqs, offsets and out_chains must be non-null");
-        return SPX_E_ARG;
-    }
-    if (nreads > PIECE_READS || (nreads && offsets[nreads] >= offsets[0] && offsets[nreads] - offsets[0] > PIECE_CHARS)) {
-        set_error("one piece per call: at most 32 Mi characters and 4 Mi reads");
-        return SPX_E_ARG;
-    }
+    if ((rc = check_batch(ix, "the chains", BATCH_MIN_LENGTH | BATCH_TEXT | BATCH_ONE_PIECE, min_length, digest_kind, want_docs,
+                          nreads && (!seqs || !offsets || !out_chains) ? "seqs, offsets and out_chains must be non-null" : nullptr, offsets,
+                          nreads)) != SPX_OK)
+        return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     product_reset(ix, ix->chain);
@@ -407,7 +382,6 @@ int spc_chain_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
                                SPX_HIP(hipMemcpyAsync(out_chains, d_out, m.nreads * sizeof(spc_chain), hipMemcpyDeviceToHost, m.stream));
                                return SPX_OK;
                            });
-    ix->mems_ready = false;  // (the records were this call's: nothing waits for spm_mems_fetch)
     if (rc != SPX_OK) return rc;
     if ((rc = product_collect(ix, ix->chain, CHAIN_WORDS, 5)) != SPX_OK) return rc;
     return chain_error_code(ix);

@@ -35,14 +35,12 @@ namespace spx {
 namespace {
 
 TraceView cigar_view(spx_index* ix) {
-    return TraceView{ix->cigar_scr,    &ix->cigar,         ix->ev_cigar,         ix->cigar_phase, ix->cigar_step_ms, ix->cigar_extra,
-                     &ix->cigar_ready, &ix->cigar_ready_n, &ix->cigar_ready_reads, nullptr,         "the CIGARs",      "spg_cigar_begin",
-                     "spg_cigar_fetch"};
+    return TraceView{ix->cigar_scr, &ix->cigar, &ix->cigar_ready, nullptr, "the CIGARs", "spg_cigar_begin", "spg_cigar_fetch"};
 }
 
 }  // namespace
 
-void release_cigar(spx_index* ix) { cigar_release(cigar_view(ix)); }
+void release_cigar(spx_index* ix) { release(ix->cigar_scr, spx_index::TB_COUNT, &ix->cigar); }
 
 }  // namespace spx
 
@@ -69,25 +67,25 @@ int spg_last_cigar_stats(spx_index* ix, spg_cigar_stats* out) {
         set_error("no CIGARs have been computed on this index yet");
         return SPX_E_ARG;
     }
-    const TraceView tv = cigar_view(ix);
-    if (ix->cigar.pending) {
-        const int rc = cigar_collect(ix, tv);
+    const spx_index::Product& p = ix->cigar;
+    if (p.pending) {
+        const int rc = product_collect(ix, ix->cigar, CIGAR_WORDS, CIGAR_WORDS, CW_ERROR);
         if (rc != SPX_OK) return rc;
     }
-    out->reads = ix->cigar.acc[0];
-    out->aligned_reads = ix->cigar.acc[1];
-    out->gaps = ix->cigar.acc[2];
-    out->filled_gaps = ix->cigar.acc[3];
-    out->cells = ix->cigar.acc[4];
-    out->entries = ix->cigar.acc[5];
-    out->path_words = ix->cigar_extra[0];
-    out->wave_fill_ticks = ix->cigar_extra[2];
-    out->wave_back_ticks = ix->cigar_extra[3];
-    out->error = (uint32_t)(ix->cigar.error & 1);
-    out->overflow = (uint32_t)((ix->cigar.error >> 1) & 1);
-    out->kernel_ms = ix->cigar.ms;
-    for (int i = 0; i < 5; ++i) out->step_ms[i] = ix->cigar_step_ms[i];
-    return cigar_error_code(tv);
+    out->reads = p.acc[0];
+    out->aligned_reads = p.acc[1];
+    out->gaps = p.acc[2];
+    out->filled_gaps = p.acc[3];
+    out->cells = p.acc[4];
+    out->entries = p.acc[CW_ENTRIES];
+    out->path_words = p.acc[CW_PATH_WORDS];
+    out->wave_fill_ticks = p.acc[CW_FILL_TICKS];
+    out->wave_back_ticks = p.acc[CW_BACK_TICKS];
+    out->error = (uint32_t)(p.error & 1);
+    out->overflow = (uint32_t)((p.error >> 1) & 1);
+    out->kernel_ms = p.ms;
+    for (int i = 0; i < 5; ++i) out->step_ms[i] = p.step_ms[i];
+    return cigar_error_code(cigar_view(ix));
 }
 
 int spg_cigar_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,

@@ -3,7 +3,8 @@
 // collects them.  The ends come in at three places, each templated or switched on `ends`: the emit lays a read's two end
 // paths and its clips around the gaps' steps (emit_read<WRITE, ENDS>), the launches call the extension's own kernels
 // through EndHooks (their sizes in the plan, their fill in front of the emit, the records' update behind the reduction),
-// and a TraceView names the scratch, the counters, the events and the waiting entries of the product that is calling.
+// and a TraceView names the scratch, the Product (counters, events, step times) and the waiting entries of the product
+// that is calling.
 // With ENDS false every kernel is the code spx_cigar.hip had.  Each translation unit gets its own copy of the kernels
 // (the library is built without relocatable device code).
 #pragma once
@@ -33,6 +34,16 @@ struct CigarCounters {  // device; zeroed in front of every launch
     unsigned long long ends, extended, band_cells, clipped;  // the extension's: spx_extend.hip
 };
 constexpr int CIGAR_WORDS = sizeof(CigarCounters) / 8;
+static_assert(CIGAR_WORDS <= spx_index::Product::WORDS, "Product::acc holds a word of every counter");
+// the words of Product::acc by name (a.reads .. a.cells are words 0 .. 4, as in the alignments), and the error word
+#define SPX_CIGAR_WORD(m) ((int)(offsetof(CigarCounters, m) / 8))
+enum {
+    CW_ERROR = SPX_CIGAR_WORD(a.error), CW_ENTRIES = SPX_CIGAR_WORD(entries), CW_PATH_WORDS = SPX_CIGAR_WORD(path_words),
+    CW_OPS_BOUND = SPX_CIGAR_WORD(ops_bound), CW_FILL_TICKS = SPX_CIGAR_WORD(fill_ticks), CW_BACK_TICKS = SPX_CIGAR_WORD(back_ticks),
+    CW_ENDS = SPX_CIGAR_WORD(ends), CW_EXTENDED = SPX_CIGAR_WORD(extended), CW_BAND_CELLS = SPX_CIGAR_WORD(band_cells),
+    CW_CLIPPED = SPX_CIGAR_WORD(clipped)
+};
+#undef SPX_CIGAR_WORD
 struct CigarArgs {
     AlignArgs a;
     uint64_t* pw;     // cap + 1: words of path per gap, then a 0
@@ -467,26 +478,17 @@ struct EndHooks {
     int (*fill)(CigarArgs& ca, const CigarPlan& plan, hipStream_t st);
     int (*finish)(CigarArgs& ca, hipStream_t st);
 };
-// The product that is calling: its scratch (TB_COUNT slots), counters, events (7, and an eighth in front of the ends'
-// fill), step times (5, and the ends' sixth), what the counters hold beyond Product::acc (4, and the ends' four) and
-// the entries that wait for its _fetch.
+// The product that is calling: its scratch (TB_COUNT slots), its counters and times, the entries that wait for its _fetch,
+// the extension's kernels and its names.  Steps: 0 plan, 1 lane fills, 2 wavefront fills, 3 emit, 4 reduce, 5 the ends.
 struct TraceView {
     spx_index::Scratch* scr;
     spx_index::Product* p;
-    hipEvent_t* ev;
-    bool* phase;
-    float* step_ms;
-    uint64_t* extra;
-    bool* ready;
-    uint64_t *ready_n, *ready_reads;
+    spx_index::Ready* ready;
     const EndHooks* ends;  // null: the CIGARs
     const char* what;  // the product in a message: "the CIGARs", "the extended CIGARs"
     const char* begin_name;
     const char* fetch_name;
 };
-inline int view_events(const TraceView& tv) { return tv.ends ? 8 : 7; }
-inline int view_steps(const TraceView& tv) { return tv.ends ? 6 : 5; }
-inline int view_extra(const TraceView& tv) { return tv.ends ? 8 : 4; }
 
 // words of trace one end needs at most: a lane owns a diagonal of the band, 16 rows a word
 inline uint64_t end_trace_words(uint32_t max_extend, uint32_t band) { return (uint64_t)((max_extend + 15) / 16) * (2 * band + 1); }
@@ -499,16 +501,6 @@ int cigar_reserve(spx_index* ix, const TraceView& tv, CigarArgs& ca, bool own_oo
     spx_index::Scratch* scr = tv.scr;
     void* p = nullptr;
     int rc;
-    if ((rc = scr[spx_index::TB_CNT].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
-    a.cnt = (uint64_t*)p;
-    if ((rc = scr[spx_index::TB_GOFFS].reserve((a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
-    a.goffs = (uint64_t*)p;
-    if ((rc = scr[spx_index::TB_GAPS].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
-    a.gaps = (uint4*)p;
-    if ((rc = scr[spx_index::TB_DESC].reserve(a.cap * 16 + 16, &p)) != SPX_OK) return rc;
-    a.desc = (ulonglong2*)p;
-    if ((rc = scr[spx_index::TB_LIST].reserve(a.cap * 4 + 16, &p)) != SPX_OK) return rc;
-    a.list = (uint32_t*)p;
     if ((rc = scr[spx_index::TB_PW].reserve((a.cap + 1) * 8, &p)) != SPX_OK) return rc;
     ca.pw = (uint64_t*)p;
     if ((rc = scr[spx_index::TB_POFFS].reserve((a.cap + 1) * 8, &p)) != SPX_OK) return rc;
@@ -530,8 +522,7 @@ int cigar_reserve(spx_index* ix, const TraceView& tv, CigarArgs& ca, bool own_oo
     ca.trace = (uint32_t*)p;
     plan->lds_global = ((size_t)a.max_fill + 1) * 4 + a.max_fill;
     plan->lds_local = plan->lds_global + TRACE_LDS_WORDS * 4;
-    size_t b1 = 0, b2 = 0, b3 = 0;
-    SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, a.cnt, a.goffs, a.nreads + 1, (hipStream_t) nullptr));
+    size_t b2 = 0, b3 = 0;
     SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, ca.pw, ca.poffs, a.cap + 1, (hipStream_t) nullptr));
     if (tv.ends) {
         if ((rc = scr[spx_index::TB_EPW].reserve((2 * a.nreads + 1) * 8, &p)) != SPX_OK) return rc;
@@ -554,9 +545,7 @@ int cigar_reserve(spx_index* ix, const TraceView& tv, CigarArgs& ca, bool own_oo
         ca.etrace = (uint32_t*)p;
         SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, ca.epw, ca.epoffs, 2 * a.nreads + 1, (hipStream_t) nullptr));
     }
-    plan->cub_bytes = std::max(std::max(b1, b2), b3);
-    if ((rc = scr[spx_index::TB_CUB].reserve(plan->cub_bytes + 16, &plan->cub)) != SPX_OK) return rc;
-    return SPX_OK;
+    return reserve_gaps(scr, a, true, true, std::max(b2, b3), &plan->cub_bytes, &plan->cub);
 }
 int cigar_reserve_path(spx_index* ix, const TraceView& tv, CigarArgs& ca, uint64_t words) {
     std::lock_guard<std::mutex> g(ix->mu);
@@ -569,12 +558,11 @@ int cigar_reserve_path(spx_index* ix, const TraceView& tv, CigarArgs& ca, uint64
     return SPX_OK;
 }
 
-// The plan on st (inside product_enqueue's launch).
+// The plan on st (inside product_enqueue's launch, which has marked step 0).
 int launch_plan(const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, hipStream_t st) {
     size_t cub_bytes = plan.cub_bytes;
     AlignArgs& a = ca.a;
     int rc;
-    SPX_HIP(hipEventRecord(tv.ev[0], st));
     const unsigned read_grid = (unsigned)((a.nreads + 1 + 255) / 256);
     k_align_count<<<read_grid, 256, 0, st>>>(a);
     SPX_HIP(hipGetLastError());
@@ -585,34 +573,37 @@ int launch_plan(const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, hipSt
     k_cigar_plan<<<(unsigned)std::min<uint64_t>((std::max<uint64_t>(a.cap + 1, a.nreads) + 255) / 256, 1024), 256, 0, st>>>(ca);
     SPX_HIP(hipGetLastError());
     SPX_HIP(hipcub::DeviceScan::ExclusiveSum(plan.cub, cub_bytes, ca.pw, ca.poffs, a.cap + 1, st));
-    SPX_HIP(hipEventRecord(tv.ev[1], st));
-    tv.phase[0] = true;
     return SPX_OK;
 }
-// The fills, the emit and the reduction on st (inside product_enqueue's launch).
-int launch_trace(const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, hipStream_t st) {
+// The step the fills, the emit and the reduction begin with: the ends' or the lane fills'.
+inline int trace_first_step(const TraceView& tv) { return tv.ends ? 5 : 1; }
+// The fills, the emit and the reduction on st (inside product_enqueue's launch).  at_open: the launch begins here and
+// product_enqueue has opened with trace_first_step, which needs no mark of its own.
+int launch_trace(const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, bool at_open, hipStream_t st) {
     size_t cub_bytes = plan.cub_bytes;
     AlignArgs& a = ca.a;
+    spx_index::Product& p = *tv.p;
+    auto begin = [&](int step) -> int { return at_open && step == trace_first_step(tv) ? SPX_OK : product_mark(p, step, st); };
     int rc;
     const unsigned read_grid = (unsigned)((a.nreads + 1 + 255) / 256);
     if (tv.ends) {
-        SPX_HIP(hipEventRecord(tv.ev[7], st));
+        if ((rc = begin(5)) != SPX_OK) return rc;
         if ((rc = tv.ends->fill(ca, plan, st)) != SPX_OK) return rc;
     }
-    SPX_HIP(hipEventRecord(tv.ev[2], st));
+    if ((rc = begin(1)) != SPX_OK) return rc;
     if (a.cap) {
         // (the number of gaps is the device's: the grid covers the capacity, and lanes past the total leave at once)
         k_trace_small<<<(unsigned)((a.cap + 255) / 256), 256, 0, st>>>(ca);
         SPX_HIP(hipGetLastError());
     }
-    SPX_HIP(hipEventRecord(tv.ev[3], st));
+    if ((rc = product_mark(p, 2, st)) != SPX_OK) return rc;
     if (a.cap) {
         k_trace_wave<false><<<(unsigned)std::min<uint64_t>(a.cap, 4096), 64, plan.lds_local, st>>>(ca);
         SPX_HIP(hipGetLastError());
         k_trace_wave<true><<<plan.grid_global, 64, plan.lds_global, st>>>(ca);
         SPX_HIP(hipGetLastError());
     }
-    SPX_HIP(hipEventRecord(tv.ev[4], st));
+    if ((rc = product_mark(p, 3, st)) != SPX_OK) return rc;
     if (tv.ends)
         k_cigar_count<true><<<read_grid, 256, 0, st>>>(ca);
     else
@@ -624,21 +615,18 @@ int launch_trace(const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, hipS
     else
         k_cigar_write<false><<<read_grid, 256, 0, st>>>(ca);
     SPX_HIP(hipGetLastError());
-    SPX_HIP(hipEventRecord(tv.ev[5], st));
+    if ((rc = product_mark(p, 4, st)) != SPX_OK) return rc;
     k_align_reduce<<<std::min(read_grid, 1024u), 256, 0, st>>>(a);
     SPX_HIP(hipGetLastError());
     if (tv.ends && (rc = tv.ends->finish(ca, st)) != SPX_OK) return rc;
-    SPX_HIP(hipEventRecord(tv.ev[6], st));
-    tv.phase[1] = true;
     return SPX_OK;
 }
 
-// One or both phases on st, between the product's two events.  Takes ix->mu.
+// One or both phases on st, between the product's two events: the time from ev0 on is the first step's of the first
+// phase there is (no step's for a batch without reads: its step times are zeros).  Takes ix->mu.
 int cigar_enqueue(spx_index* ix, const TraceView& tv, CigarArgs& ca, const CigarPlan& plan, bool first, bool second, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    for (int i = 0; i < view_events(tv); ++i)
-        if (!tv.ev[i]) SPX_HIP(hipEventCreate(&tv.ev[i]));
     return product_enqueue(*tv.p, CIGAR_WORDS, st, [&](void* counters) -> int {
         ca.c = (CigarCounters*)counters;
         ca.a.c = &ca.c->a;
@@ -648,54 +636,9 @@ int cigar_enqueue(spx_index* ix, const TraceView& tv, CigarArgs& ca, const Cigar
             return SPX_OK;
         }
         if (first && (rc = launch_plan(tv, ca, plan, st)) != SPX_OK) return rc;
-        if (second && (rc = launch_trace(tv, ca, plan, st)) != SPX_OK) return rc;
+        if (second && (rc = launch_trace(tv, ca, plan, !first, st)) != SPX_OK) return rc;
         return SPX_OK;
-    });
-}
-// Waits for what was enqueued last and adds its counters and times to the call's.  Takes ix->mu.
-int cigar_collect(spx_index* ix, const TraceView& tv) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    spx_index::Product& p = *tv.p;
-    SPX_HIP(hipEventSynchronize(p.ev1));
-    CigarCounters c;
-    SPX_HIP(hipMemcpy(&c, p.counters.p, sizeof c, hipMemcpyDeviceToHost));
-    float ms = 0;
-    SPX_HIP(hipEventElapsedTime(&ms, p.ev0, p.ev1));
-    p.ms += ms;
-    p.acc[0] += c.a.reads;
-    p.acc[1] += c.a.aligned;
-    p.acc[2] += c.a.gaps;
-    p.acc[3] += c.a.filled;
-    p.acc[4] += c.a.cells;
-    p.acc[5] += c.entries;
-    p.error |= c.a.error;
-    tv.extra[0] += c.path_words;
-    tv.extra[1] += c.ops_bound;
-    tv.extra[2] += c.fill_ticks;
-    tv.extra[3] += c.back_ticks;
-    if (tv.ends) {
-        tv.extra[4] += c.ends;
-        tv.extra[5] += c.extended;
-        tv.extra[6] += c.band_cells;
-        tv.extra[7] += c.clipped;
-    }
-    p.pending = false;
-    hipEvent_t* e = tv.ev;
-    if (tv.phase[0]) SPX_HIP(hipEventElapsedTime(&tv.step_ms[0], e[0], e[1]));
-    if (tv.phase[1]) {
-        for (int i = 1; i < 5; ++i) SPX_HIP(hipEventElapsedTime(&tv.step_ms[i], e[i + 1], e[i + 2]));
-        if (tv.ends) SPX_HIP(hipEventElapsedTime(&tv.step_ms[5], e[7], e[2]));
-    }
-    tv.phase[0] = tv.phase[1] = false;
-    return SPX_OK;
-}
-void cigar_reset(spx_index* ix, const TraceView& tv) {
-    product_reset(ix, *tv.p);
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(tv.extra, 0, view_extra(tv) * sizeof(uint64_t));
-    std::memset(tv.step_ms, 0, view_steps(tv) * sizeof(float));
-    tv.phase[0] = tv.phase[1] = false;
+    }, !ca.a.nreads ? -1 : first ? 0 : trace_first_step(tv));
 }
 int cigar_error_code(const TraceView& tv) {
     if (tv.p->error & 1) {
@@ -706,13 +649,6 @@ int cigar_error_code(const TraceView& tv) {
         return SPX_E_FORMAT;
     }
     return SPX_OK;
-}
-void cigar_release(const TraceView& tv) {
-    for (int i = 0; i < spx_index::TB_COUNT; ++i)
-        if (tv.scr[i].p) (void)hipFree(tv.scr[i].p);
-    for (int i = 0; i < view_events(tv); ++i)
-        if (tv.ev[i]) (void)hipEventDestroy(tv.ev[i]);
-    product_release(*tv.p);
 }
 
 // What the four parameters of the extension are to the kernels (zeros for the CIGARs) and the ends a caller asked for.
@@ -756,7 +692,7 @@ int trace_device(spx_index* ix, const TraceView& tv, const uint8_t* d_reads, con
                             "the 64-bit arrays 8-byte, d_pred and d_out_ops 4-byte aligned");
         return SPX_E_ARG;
     }
-    cigar_reset(ix, tv);
+    product_reset(ix, *tv.p);
     CigarArgs ca{};
     AlignArgs& a = ca.a;
     a.R = d_reads;
@@ -792,43 +728,23 @@ int trace_begin(spx_index* ix, const TraceView& tv, int digest_kind, uint32_t k,
                 uint64_t nreads, uint64_t min_length, int want_docs, const spc_params* chain_params, const spa_params* align_params,
                 const EndParams& ep, spa_alignment* out_alignments, spc_chain* out_chains, uint64_t* out_values, void* out_ends,
                 uint64_t* n_entries) {
-    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
     int rc;
     if ((rc = chain_check_params(ix, chain_params)) != SPX_OK) return rc;
-    if (min_length == 0) {
-        set_error("min_length must be at least 1: a position of length 0 matches nothing");
-        return SPX_E_ARG;
-    }
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
-    if (!ix->has_samples || !ix->text) {
-        set_error("%s need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)", tv.what);
-        return SPX_E_ARG;
-    }
-    if (want_docs && !ix->has_docs) {
-        set_error("document ids requested but the index has no document array");
-        return SPX_E_ARG;
-    }
-    if (!n_entries || (nreads && (!seqs || !offsets || !out_alignments))) {
-        set_error("seqs, offsets, out_alignments and n_entries must be non-null");
-        return SPX_E_ARG;
-    }
-    if (nreads > PIECE_READS || (nreads && offsets[nreads] >= offsets[0] && offsets[nreads] - offsets[0] > PIECE_CHARS)) {
-        set_error("one piece per call: at most 32 Mi characters and 4 Mi reads");
-        return SPX_E_ARG;
-    }
+    if ((rc = check_batch(ix, tv.what, BATCH_MIN_LENGTH | BATCH_TEXT | BATCH_ONE_PIECE, min_length, digest_kind, want_docs,
+                          !n_entries || (nreads && (!seqs || !offsets || !out_alignments))
+                              ? "seqs, offsets, out_alignments and n_entries must be non-null"
+                              : nullptr,
+                          offsets, nreads)) != SPX_OK)
+        return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
-    cigar_reset(ix, tv);
+    product_reset(ix, *tv.p);
     product_reset(ix, ix->chain);
-    *tv.ready = false;
+    tv.ready->ok = false;
     *n_entries = 0;
     if (nreads == 0) {
         tv.p->have = ix->chain.have = true;  // (the stats of an empty batch are zeros)
-        *tv.ready = true;
-        *tv.ready_n = *tv.ready_reads = 0;
+        ready_publish(*tv.ready, 0, 0);
         return SPX_OK;
     }
     spx_index::Scratch* scr = tv.scr;
@@ -868,9 +784,9 @@ int trace_begin(spx_index* ix, const TraceView& tv, int digest_kind, uint32_t k,
             if ((r = cigar_enqueue(ix, tv, ca, plan, true, false, m.stream)) != SPX_OK) return r;
             // the one wait that spa_align_batch does not have: the path's words and the bound of the entries are the
             // device's, and both buffers have their size before the fills are enqueued
-            if ((r = cigar_collect(ix, tv)) != SPX_OK) return r;
-            if ((r = cigar_reserve_path(ix, tv, ca, tv.extra[0])) != SPX_OK) return r;
-            ca.op_cap = std::min<uint64_t>(tv.extra[1], 0xffffffffull);
+            if ((r = product_collect(ix, *tv.p, CIGAR_WORDS, CIGAR_WORDS, CW_ERROR)) != SPX_OK) return r;
+            if ((r = cigar_reserve_path(ix, tv, ca, tv.p->acc[CW_PATH_WORDS])) != SPX_OK) return r;
+            ca.op_cap = std::min<uint64_t>(tv.p->acc[CW_OPS_BOUND], 0xffffffffull);
             void* d_ops = nullptr;
             if ((r = scr[spx_index::TB_OPS].reserve(ca.op_cap * 4 + 16, &d_ops)) != SPX_OK) return r;
             ca.ops = (uint32_t*)d_ops;
@@ -881,42 +797,23 @@ int trace_begin(spx_index* ix, const TraceView& tv, int digest_kind, uint32_t k,
             if (d_ends) SPX_HIP(hipMemcpyAsync(out_ends, d_ends, m.nreads * 32, hipMemcpyDeviceToHost, m.stream));
             return SPX_OK;
         });
-    ix->mems_ready = false;  // (the records were this call's: nothing waits for spm_mems_fetch)
     if (rc != SPX_OK) return rc;
     spc_chain_stats cs;
     if ((rc = spc_last_chain_stats(ix, &cs)) != SPX_OK) return rc;
-    if ((rc = cigar_collect(ix, tv)) != SPX_OK) return rc;
+    if ((rc = product_collect(ix, *tv.p, CIGAR_WORDS, CIGAR_WORDS, CW_ERROR)) != SPX_OK) return rc;
     if ((rc = cigar_error_code(tv)) != SPX_OK) return rc;
     if (tv.p->error & 2) {
         set_error("internal: the bound of the entries did not hold");
         return SPX_E_FORMAT;
     }
-    *tv.ready = true;
-    *tv.ready_n = tv.p->acc[5];
-    *tv.ready_reads = nreads;
-    *n_entries = *tv.ready_n;
+    *n_entries = tv.p->acc[CW_ENTRIES];
+    ready_publish(*tv.ready, *n_entries, nreads);
     return SPX_OK;
 }
 
 int trace_fetch(spx_index* ix, const TraceView& tv, uint64_t* out_op_offsets, uint32_t* out_ops) {
-    std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (!*tv.ready) {
-        set_error("%s without a successful %s before it", tv.fetch_name, tv.begin_name);
-        return SPX_E_ARG;
-    }
-    if (!out_op_offsets || (*tv.ready_n && !out_ops)) {
-        set_error("out_op_offsets and out_ops must be non-null");
-        return SPX_E_ARG;
-    }
-    *tv.ready = false;
-    if (*tv.ready_reads == 0) {
-        out_op_offsets[0] = 0;
-        return SPX_OK;
-    }
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipMemcpy(out_op_offsets, tv.scr[spx_index::TB_OOFFS].p, (*tv.ready_reads + 1) * 8, hipMemcpyDeviceToHost));
-    if (*tv.ready_n) SPX_HIP(hipMemcpy(out_ops, tv.scr[spx_index::TB_OPS].p, *tv.ready_n * 4, hipMemcpyDeviceToHost));
-    return SPX_OK;
+    return ready_fetch(ix, *tv.ready, tv.scr[spx_index::TB_OOFFS], tv.scr[spx_index::TB_OPS], tv.fetch_name, tv.begin_name, out_op_offsets,
+                       out_ops);
 }
 
 }  // namespace

@@ -528,11 +528,7 @@ int cover_add_batch_with(spx_index* ix, const char* who, int digest_kind, uint32
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     // (another host thread on this handle between the two locks would have taken the entries, or the arrays)
-    if (!ix->map_ready || ix->map_ready_reads != nreads || ix->map_ready_n != n_in) {
-        set_error("%s: another call on this index took the mappings: calls on one handle must not overlap", who);
-        return SPX_E_ARG;
-    }
-    ix->map_ready = false;  // (the entries are this call's: nothing waits for spn_map_fetch)
+    if ((rc = ready_take(ix->map_ready, nreads, n_in, who, "the mappings")) != SPX_OK) return rc;
     if ((rc = cover_need_arrays(ix, who)) != SPX_OK) return rc;
     if (nreads == 0) return SPX_OK;
     uint64_t mapped = 0;

@@ -467,11 +467,7 @@ int check_index(const spx_index* ix) {
 
 }  // namespace
 
-void release_votes(spx_index* ix) {
-    for (auto& sc : ix->vote_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    product_release(ix->votes);
-}
+void release_votes(spx_index* ix) { release(ix->vote_scr, spx_index::V_COUNT, &ix->votes); }
 
 }  // namespace spx
 
@@ -536,10 +532,7 @@ int spv_assign_batch(spx_index* ix, int mode, int digest_kind, uint32_t k, uint3
         set_error("mode must be SPX_MODE_PML or SPX_MODE_MS");
         return SPX_E_ARG;
     }
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
+    if ((rc = check_digest_kind(digest_kind)) != SPX_OK) return rc;
     if (mode == SPX_MODE_MS && (!ix->has_samples || !ix->text)) {
         set_error("MS mode needs an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text): "
                   "the votes go by the MS lengths");

@@ -363,9 +363,7 @@ int hook_finish(CigarArgs& ca, hipStream_t st) {
 const EndHooks HOOKS{hook_plan, hook_fill, hook_finish};
 
 TraceView extend_view(spx_index* ix) {
-    return TraceView{ix->extend_scr,    &ix->extend,         ix->ev_extend,          ix->extend_phase, ix->extend_step_ms, ix->extend_extra,
-                     &ix->extend_ready, &ix->extend_ready_n, &ix->extend_ready_reads, &HOOKS,           "the extended CIGARs", "spe_extend_begin",
-                     "spe_extend_fetch"};
+    return TraceView{ix->extend_scr, &ix->extend, &ix->extend_ready, &HOOKS, "the extended CIGARs", "spe_extend_begin", "spe_extend_fetch"};
 }
 
 int check_extend_params(const spe_params* p, EndParams* ep) {
@@ -394,7 +392,7 @@ int check_extend_params(const spe_params* p, EndParams* ep) {
 
 }  // namespace
 
-void release_extend(spx_index* ix) { cigar_release(extend_view(ix)); }
+void release_extend(spx_index* ix) { release(ix->extend_scr, spx_index::TB_COUNT, &ix->extend); }
 
 }  // namespace spx
 
@@ -423,28 +421,28 @@ int spe_last_extend_stats(spx_index* ix, spe_extend_stats* out) {
         set_error("no extended CIGARs have been computed on this index yet");
         return SPX_E_ARG;
     }
-    const TraceView tv = extend_view(ix);
-    if (ix->extend.pending) {
-        const int rc = cigar_collect(ix, tv);
+    const spx_index::Product& p = ix->extend;
+    if (p.pending) {
+        const int rc = product_collect(ix, ix->extend, CIGAR_WORDS, CIGAR_WORDS, CW_ERROR);
         if (rc != SPX_OK) return rc;
     }
-    out->reads = ix->extend.acc[0];
-    out->aligned_reads = ix->extend.acc[1];
-    out->gaps = ix->extend.acc[2];
-    out->filled_gaps = ix->extend.acc[3];
-    out->cells = ix->extend.acc[4];
-    out->entries = ix->extend.acc[5];
-    out->path_words = ix->extend_extra[0];
-    out->ends = ix->extend_extra[4];
-    out->extended_ends = ix->extend_extra[5];
-    out->band_cells = ix->extend_extra[6];
-    out->clipped = ix->extend_extra[7];
-    out->error = (uint32_t)(ix->extend.error & 1);
-    out->overflow = (uint32_t)((ix->extend.error >> 1) & 1);
-    out->kernel_ms = ix->extend.ms;
-    for (int i = 0; i < 6; ++i) out->step_ms[i] = ix->extend_step_ms[i];
+    out->reads = p.acc[0];
+    out->aligned_reads = p.acc[1];
+    out->gaps = p.acc[2];
+    out->filled_gaps = p.acc[3];
+    out->cells = p.acc[4];
+    out->entries = p.acc[CW_ENTRIES];
+    out->path_words = p.acc[CW_PATH_WORDS];
+    out->ends = p.acc[CW_ENDS];
+    out->extended_ends = p.acc[CW_EXTENDED];
+    out->band_cells = p.acc[CW_BAND_CELLS];
+    out->clipped = p.acc[CW_CLIPPED];
+    out->error = (uint32_t)(p.error & 1);
+    out->overflow = (uint32_t)((p.error >> 1) & 1);
+    out->kernel_ms = p.ms;
+    for (int i = 0; i < 6; ++i) out->step_ms[i] = p.step_ms[i];
     out->reserved = 0;
-    return cigar_error_code(tv);
+    return cigar_error_code(extend_view(ix));
 }
 
 int spe_extend_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const uint8_t* seqs, const uint64_t* offsets,

@@ -277,35 +277,42 @@ struct spx_index {
     enum { G_RAW, G_OFFS, G_DIG, G_DIG_OFFS, G_LEN, G_DOC, G_PTR, G_SET_STRIDE, G_COUNT = 2 * G_SET_STRIDE };
     Scratch stage_scr[G_COUNT];
     hipStream_t stage_s[2] = {nullptr, nullptr};
-    // What a product's kernels count (product_enqueue / product_collect below, under mu): the device words they count in,
-    // zeroed in front of every launch -- the words that add up first, the error bits last --, the events around the
-    // kernels of the last call and the stream they ran on, and what the call has counted so far.
+    // What a product's kernels count and how long they take (product_open .. product_collect below, under mu): the device
+    // words they count in, zeroed in front of every launch; the events around the kernels enqueued last, the marks between
+    // them -- from mark i on the time belongs to step label[i], from ev0 on to step label0, -1: to none -- and the stream
+    // they ran on; and what the call has collected so far: acc[i] is the sum of word i (the error word's stays 0), error
+    // the OR of the error word, ms the time between ev0 and ev1, step_ms the time of every labelled step.
     struct Product {
+        static constexpr int WORDS = 17, MARKS = 6, STEPS = 6;  // (the extended CIGARs' counters, marks and steps)
         Scratch counters;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mark[MARKS] = {};
+        int label0 = -1, label[MARKS] = {}, nmarks = 0;
         hipStream_t stream = nullptr;
         bool have = false, pending = false;
-        uint64_t acc[6] = {};
+        uint64_t acc[WORDS] = {};
         uint64_t error = 0;
-        float ms = 0;
+        float ms = 0, step_ms[STEPS] = {};
+    };
+    // The records of a _begin that wait on the device for its _fetch, or for the product that goes on from them
+    // (ready_publish / ready_take / ready_fetch below, under host_mu): n entries of `reads` reads.
+    struct Ready {
+        bool ok = false;
+        uint64_t n = 0, reads = 0;
     };
     // document votes (spx_docvote.hip): read lists and the long reads' tables (under mu), then the records of the staged
     // walk's two buffer sets (under host_mu)
     enum { V_MEDIUM, V_LONG, V_TILES, V_ACC, V_TABLE, V_OUT0, V_COUNT = V_OUT0 + 2 };
     Scratch vote_scr[V_COUNT];
     Product votes;  // acc: reads short, medium, long, empty; voting positions; tiles
-    // matches (spx_mems.hip): counters, the bitmap of reported starts, its prefix sums and the scan's space (under mu),
-    // then spm_mems_begin's match offsets (under host_mu); the events around the count and the write kernels of the last
-    // call -- two intervals with a host wait between them --, what that call counted, and the records that wait for
-    // spm_mems_fetch
-    enum { M_COUNTERS, M_BITS, M_PREFIX, M_CUB, M_MOFFS, M_OUT, M_OUT_DOCS, M_COUNT };
+    // matches (spx_mems.hip): the bitmap of reported starts, its prefix sums and the scan's space (under mu), then
+    // spm_mems_begin's match offsets (under host_mu); the capacity of the last call; and the records that wait for
+    // spm_mems_fetch (reads: unused), with or without their document ids
+    enum { M_BITS, M_PREFIX, M_CUB, M_MOFFS, M_OUT, M_OUT_DOCS, M_COUNT };
     Scratch mems_scr[M_COUNT];
-    hipEvent_t ev_m[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t mems_stream = nullptr;
-    bool have_mems = false, mems_pending = false, mems_ready = false, mems_ready_docs = false;
-    uint64_t mems_capacity = 0, mems_ready_n = 0;
-    uint64_t mems_acc[4] = {};  // values, matches, longest, error bits
-    float mems_ms = 0;
+    Product mems;  // acc: values, matches, longest; steps: count, write -- two intervals, in the host form with a wait between
+    uint64_t mems_capacity = 0;
+    Ready mems_ready;
+    bool mems_ready_docs = false;
     // placements (spx_place.hip): the records of the staged walk's two buffer sets (under host_mu)
     Scratch place_scr[2];
     Product place;  // acc: values, placed, seed values, extended values
@@ -315,59 +322,38 @@ struct spx_index {
     Product chain;  // acc: reads, anchors, chained reads, chain anchors, candidates
     // alignments (spx_align.hip): the gap counts, their offsets, the per-gap table, where each gap's strings start, the list
     // of the gaps that take a wavefront and the scan's space (under mu), then spa_align_batch's chain records, its
-    // alignments and pred (under host_mu); the events between the four steps of the last call and their times
+    // alignments and pred (under host_mu)
     enum { L_CNT, L_GOFFS, L_GAPS, L_DESC, L_LIST, L_CUB, L_CHAINS, L_OUT, L_PRED, L_COUNT };
     Scratch align_scr[L_COUNT];
-    Product align;  // acc: reads, aligned reads, gaps, filled gaps, cells
-    hipEvent_t ev_align[3] = {nullptr, nullptr, nullptr};
-    bool align_steps = false;
-    float align_step_ms[4] = {};
-    // CIGARs (spx_cigar.hip): the scratch of the shared count, walk and reduce as above, the list of the gaps that take a
-    // wavefront (two kinds, from either end), each gap's words of path and their offsets, the path, the wavefronts' trace
-    // buffers and the reads' entry counts (under mu), then spg_cigar_begin's chain records, alignments, pred, op offsets
-    // and entries (under host_mu); the events around the steps of the last call and their times; what the counters hold
-    // beyond Product::acc (path words, the bound of the entries, the ticks of fill and walk back); and the entries that
-    // wait for spg_cigar_fetch
+    Product align;  // acc: reads, aligned reads, gaps, filled gaps, cells; steps: count and scan, walk, fill, reduce
+    // CIGARs (spx_cigar.hip): the scratch of the shared count, walk and reduce in the slots they have above, the list of the
+    // gaps that take a wavefront (two kinds, from either end), each gap's words of path and their offsets, the path, the
+    // wavefronts' trace buffers and the reads' entry counts (under mu), then spg_cigar_begin's chain records, alignments,
+    // pred, op offsets and entries (under host_mu); and the entries that wait for spg_cigar_fetch
     enum { TB_CNT, TB_GOFFS, TB_GAPS, TB_DESC, TB_LIST, TB_CUB, TB_PW, TB_POFFS, TB_PATH, TB_TRACE, TB_OCNT, TB_CHAINS, TB_OUT,
            TB_PRED, TB_OOFFS, TB_OPS, TB_EPW, TB_EPOFFS, TB_ERES, TB_ETRACE, TB_ENDS, TB_COUNT };
     Scratch cigar_scr[TB_COUNT];
-    Product cigar;  // acc: reads, aligned reads, gaps, filled gaps, cells, entries
-    hipEvent_t ev_cigar[7] = {};
-    bool cigar_phase[2] = {false, false};  // the events of the plan / of the other steps were recorded by the last call
-    float cigar_step_ms[5] = {};
-    uint64_t cigar_extra[4] = {};
-    bool cigar_ready = false;
-    uint64_t cigar_ready_n = 0, cigar_ready_reads = 0;
+    Product cigar;  // acc: the words of CigarCounters; steps: plan, lane fills, wavefront fills, emit, reduce
+    Ready cigar_ready;
     // extended CIGARs (spx_extend.hip): the same set once more, the product's own (both drive the code of
     // spx_cigar_kernels.h through a TraceView), with the slots only this product fills: each end's words of path and their
     // offsets, the ends' results, the trace buffers of the ends' wavefronts (under mu) and spe_extend_begin's ends (under
-    // host_mu); an eighth event in front of the ends' step, its time, and the ends' four counters
+    // host_mu)
     Scratch extend_scr[TB_COUNT];
-    Product extend;  // acc: as cigar's
-    hipEvent_t ev_extend[8] = {};
-    bool extend_phase[2] = {false, false};
-    float extend_step_ms[6] = {};
-    uint64_t extend_extra[8] = {};
-    bool extend_ready = false;
-    uint64_t extend_ready_n = 0, extend_ready_reads = 0;
+    Product extend;  // acc: as cigar's; steps: cigar's five, then the ends (which run between plan and lane fills)
+    Ready extend_ready;
     // mappings (spx_map.hip): the piece starts P[0 .. map_pieces] on the device beside the index -- this handle's own
     // copy, a clone has another -- and the lengths they came from; each read's plan, entry count and the scan's space
-    // (under mu), then spn_map_begin's read offsets, records, op offsets and entries (under host_mu); the event between
-    // the two steps of the last call and their times; what that call counted (reads, mapped, cut, reverse, entries in
-    // and out, characters cut, error bits); and the entries that wait for spn_map_fetch
+    // (under mu), then spn_map_begin's read offsets, records, op offsets and entries (under host_mu); and the entries that
+    // wait for spn_map_fetch
     uint64_t* map_P = nullptr;
     uint64_t map_pieces = 0;
     uint32_t map_strands = 0;
     std::vector<uint64_t> map_seq_lengths;
     enum { N_PLAN, N_OCNT, N_CUB, N_ROFFS, N_OUT, N_OOFFS, N_OPS, N_COUNT };
     Scratch map_scr[N_COUNT];
-    Product map;  // (acc unused: map_acc)
-    hipEvent_t ev_map = nullptr;
-    bool map_steps = false;
-    float map_step_ms[2] = {};
-    uint64_t map_acc[8] = {};
-    bool map_ready = false;
-    uint64_t map_ready_n = 0, map_ready_reads = 0;
+    Product map;  // acc: reads, mapped, cut, reverse, entries in and out, characters cut; steps: locate and count, write
+    Ready map_ready;
     // What the coverage and the pileup keep alike (spx_genome_kernels.h): one Product per step -- add, finish, output --; the
     // shared scratch: the list of the reads that take a wavefront, the scans' space, the output's tile counts and offsets
     // (under mu), its count word and records (under host_mu); from S_OWN on the product's own, first the ARRAYS arrays a
@@ -494,28 +480,41 @@ int stage_plan(spx_index* ix, const StageJob& job, StagePlan* plan);
 int stage_streams(spx_index* ix, hipStream_t out[2]);  // the two streams of the pieces (created on first use)
 int stage_run(spx_index* ix, const StageJob& job, const StagePlan& plan);
 void release_stage(spx_index* ix);
-// A product's kernels between its two events.  The caller holds ix->mu and has set the device; `launch` gets the zeroed
-// counters.  The counters and the events are the index's: a call on another stream waits for the one before.
-template <typename Launch>
-int product_enqueue(spx_index::Product& p, size_t words, hipStream_t st, Launch&& launch) {
-    if (!p.ev0) SPX_HIP(hipEventCreate(&p.ev0));
-    if (!p.ev1) SPX_HIP(hipEventCreate(&p.ev1));
+// A product's kernels between its two events: open, the launches with a mark wherever the next step begins, close.  The
+// caller holds ix->mu and has set the device.  The counters and the events are the index's: a call on another stream
+// waits for the one before.  open zeroes the counters (*c) and records ev0; the time from there on belongs to `step`.
+int product_open(spx_index::Product& p, size_t words, hipStream_t st, int step, void** c);
+// from here on the time belongs to `step`: -1 (to none) .. Product::STEPS - 1
+int product_mark(spx_index::Product& p, int step, hipStream_t st);
+int product_close(spx_index::Product& p, hipStream_t st);
+template <typename Launch>  // `launch` gets the zeroed counters
+int product_enqueue(spx_index::Product& p, size_t words, hipStream_t st, Launch&& launch, int step = -1) {
     void* c = nullptr;
     int rc;
-    if ((rc = p.counters.reserve(words * 8, &c)) != SPX_OK) return rc;
-    if (p.have && p.stream != st) SPX_HIP(hipStreamWaitEvent(st, p.ev1, 0));
-    SPX_HIP(hipMemsetAsync(c, 0, words * 8, st));
-    SPX_HIP(hipEventRecord(p.ev0, st));
-    if ((rc = launch(c)) != SPX_OK) return rc;
-    SPX_HIP(hipEventRecord(p.ev1, st));
-    p.have = p.pending = true;
-    p.stream = st;
-    return SPX_OK;
+    if ((rc = product_open(p, words, st, step, &c)) != SPX_OK || (rc = launch(c)) != SPX_OK) return rc;
+    return product_close(p, st);
 }
-// waits for the kernels enqueued last and adds their first `nacc` words to p.acc, their last to p.error.  Takes ix->mu.
-int product_collect(spx_index* ix, spx_index::Product& p, int words, int nacc);
+// waits for the kernels enqueued last; adds their first `nacc` words to p.acc but word `error_word` (-1: the last), which
+// is ORed into p.error; adds the time between the two events to p.ms and the time of every labelled step to its
+// p.step_ms.  Takes ix->mu.
+int product_collect(spx_index* ix, spx_index::Product& p, int words, int nacc, int error_word = -1);
 void product_reset(spx_index* ix, spx_index::Product& p);
 void product_release(spx_index::Product& p);
+void release(spx_index::Scratch* scr, int n, spx_index::Product* p);  // frees scr[0 .. n) and, unless null, releases *p
+// The fetch slot.  publish and take: the caller holds host_mu.  take: the records `whose` left for `who` are still there
+// -- `reads` reads, n entries -- and are `who`'s from here on: nothing waits for the fetch.  fetch TAKES host_mu itself
+// (it is the whole body of a _fetch): the op offsets and the entries from their two scratch slots to the caller's arrays.
+inline void ready_publish(spx_index::Ready& r, uint64_t n, uint64_t reads) { r = spx_index::Ready{true, n, reads}; }
+int ready_take(spx_index::Ready& r, uint64_t reads, uint64_t n, const char* who, const char* whose);
+int ready_fetch(spx_index* ix, spx_index::Ready& r, const spx_index::Scratch& op_offsets, const spx_index::Scratch& ops,
+                const char* fetch_name, const char* begin_name, uint64_t* out_op_offsets, uint32_t* out_ops);
+int check_digest_kind(int digest_kind);  // 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA, else SPX_E_ARG and the message
+// The argument checks the host forms share, in the order they report: min_length (BATCH_MIN_LENGTH), digest_kind, the SA
+// samples and the text that `what` ("the chains") need (BATCH_TEXT), the document array (want_docs), the caller's own
+// pointers (null_pointers: the message when one of them is null, else null) and the one piece (BATCH_ONE_PIECE).
+enum { BATCH_MIN_LENGTH = 1, BATCH_TEXT = 2, BATCH_ONE_PIECE = 4 };
+int check_batch(const spx_index* ix, const char* what, int flags, uint64_t min_length, int digest_kind, int want_docs,
+                const char* null_pointers, const uint64_t* offsets, uint64_t nreads);
 // spx_docvote.hip: frees what the document votes hold of the device (spx_index_free)
 void release_votes(spx_index* ix);
 // spx_mems.hip: the same for the matches

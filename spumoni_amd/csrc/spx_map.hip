@@ -300,15 +300,8 @@ __global__ __launch_bounds__(256) void k_map_write(MapArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.c->reads = a.nreads;
 }
 
-void map_reset(spx_index* ix) {
-    product_reset(ix, ix->map);
-    std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->map_acc, 0, sizeof ix->map_acc);
-    ix->map_step_ms[0] = ix->map_step_ms[1] = 0;
-    ix->map_steps = false;
-}
-
-// The scratch of one call and both kernels on st, between the product's two events.  Takes ix->mu.
+// The scratch of one call and both kernels on st, between the product's two events, with a mark where the second step
+// begins (none for a batch without reads: its step times are zeros).  Takes ix->mu.
 int map_enqueue(spx_index* ix, MapArgs& a, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
@@ -325,7 +318,6 @@ int map_enqueue(spx_index* ix, MapArgs& a, hipStream_t st) {
     SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, a.ocnt, a.ooffs, a.nreads + 1, (hipStream_t) nullptr));
     void* cub = nullptr;
     if ((rc = ix->map_scr[spx_index::N_CUB].reserve(cub_bytes + 16, &cub)) != SPX_OK) return rc;
-    if (!ix->ev_map) SPX_HIP(hipEventCreate(&ix->ev_map));
     return product_enqueue(ix->map, MAP_WORDS, st, [&](void* counters) -> int {
         a.c = (MapCounters*)counters;
         if (!a.nreads) {
@@ -336,34 +328,11 @@ int map_enqueue(spx_index* ix, MapArgs& a, hipStream_t st) {
         k_map_count<<<grid, 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
         SPX_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, a.ocnt, a.ooffs, a.nreads + 1, st));
-        SPX_HIP(hipEventRecord(ix->ev_map, st));
+        if ((rc = product_mark(ix->map, 1, st)) != SPX_OK) return rc;
         k_map_write<<<std::min(grid, 1024u), 256, 0, st>>>(a);
         SPX_HIP(hipGetLastError());
-        ix->map_steps = true;
         return SPX_OK;
-    });
-}
-
-// Waits for what was enqueued last and takes its counters and times.  Takes ix->mu.
-int map_collect(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    spx_index::Product& p = ix->map;
-    SPX_HIP(hipEventSynchronize(p.ev1));
-    unsigned long long c[MAP_WORDS];
-    SPX_HIP(hipMemcpy(c, p.counters.p, sizeof c, hipMemcpyDeviceToHost));
-    float ms = 0;
-    SPX_HIP(hipEventElapsedTime(&ms, p.ev0, p.ev1));
-    p.ms += ms;
-    for (int i = 0; i < MAP_WORDS - 1; ++i) ix->map_acc[i] += c[i];
-    p.error |= c[MAP_WORDS - 1];
-    if (ix->map_steps) {
-        SPX_HIP(hipEventElapsedTime(&ix->map_step_ms[0], p.ev0, ix->ev_map));
-        SPX_HIP(hipEventElapsedTime(&ix->map_step_ms[1], ix->ev_map, p.ev1));
-    }
-    ix->map_steps = false;
-    p.pending = false;
-    return SPX_OK;
+    }, a.nreads ? 0 : -1);
 }
 
 int map_error_code(const spx_index* ix) {
@@ -391,10 +360,7 @@ int need_table(const spx_index* ix, const char* who) {
 
 void release_map(spx_index* ix) {
     if (ix->map_P) (void)hipFree(ix->map_P);
-    for (auto& sc : ix->map_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    if (ix->ev_map) (void)hipEventDestroy(ix->ev_map);
-    product_release(ix->map);
+    release(ix->map_scr, spx_index::N_COUNT, &ix->map);
 }
 
 int clone_map(spx_index* src, spx_index* ix) {
@@ -464,7 +430,7 @@ int spn_set_sequences(spx_index* ix, const uint64_t* seq_lengths, uint64_t n_seq
     ix->map_pieces = P.size() - 1;
     ix->map_strands = strands;
     ix->map_seq_lengths.assign(seq_lengths, seq_lengths + n_seqs);
-    ix->map_ready = false;
+    ix->map_ready.ok = false;
     cover_table_changed(ix);
     call_table_changed(ix);
     return SPX_OK;
@@ -491,7 +457,7 @@ int spn_map_device(spx_index* ix, const spa_alignment* d_alignments, const uint6
                   "arrays 8-byte, d_ops and d_out_ops 4-byte aligned");
         return SPX_E_ARG;
     }
-    map_reset(ix);
+    product_reset(ix, ix->map);
     MapArgs a{};
     a.rec = (const uint4*)d_alignments;
     a.ioffs = d_op_offsets;
@@ -515,22 +481,23 @@ int spn_last_map_stats(spx_index* ix, spn_map_stats* out) {
         set_error("no mappings have been computed on this index yet");
         return SPX_E_ARG;
     }
-    if (ix->map.pending) {
-        const int rc = map_collect(ix);
+    const spx_index::Product& p = ix->map;
+    if (p.pending) {
+        const int rc = product_collect(ix, ix->map, MAP_WORDS, MAP_WORDS - 1);
         if (rc != SPX_OK) return rc;
     }
-    out->reads = ix->map_acc[0];
-    out->mapped = ix->map_acc[1];
-    out->cut_reads = ix->map_acc[2];
-    out->reverse_reads = ix->map_acc[3];
-    out->entries_in = ix->map_acc[4];
-    out->entries_out = ix->map_acc[5];
-    out->cut_chars = ix->map_acc[6];
-    out->error = (uint32_t)(ix->map.error & 1);
-    out->overflow = (uint32_t)((ix->map.error >> 1) & 1);
-    out->kernel_ms = ix->map.ms;
-    out->step_ms[0] = ix->map_step_ms[0];
-    out->step_ms[1] = ix->map_step_ms[1];
+    out->reads = p.acc[0];
+    out->mapped = p.acc[1];
+    out->cut_reads = p.acc[2];
+    out->reverse_reads = p.acc[3];
+    out->entries_in = p.acc[4];
+    out->entries_out = p.acc[5];
+    out->cut_chars = p.acc[6];
+    out->error = (uint32_t)(p.error & 1);
+    out->overflow = (uint32_t)((p.error >> 1) & 1);
+    out->kernel_ms = p.ms;
+    out->step_ms[0] = p.step_ms[0];
+    out->step_ms[1] = p.step_ms[1];
     out->reserved = 0;
     return map_error_code(ix);
 }
@@ -558,18 +525,12 @@ int spn_map_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const 
         return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
-    // (another host thread on this handle between the two locks would have taken the entries or replaced them)
-    if (!ix->extend_ready || ix->extend_ready_reads != nreads || ix->extend_ready_n != n_in) {
-        set_error("spn_map_begin: another call on this index took the extended CIGARs: calls on one handle must not overlap");
-        return SPX_E_ARG;
-    }
-    ix->extend_ready = false;  // (the entries are this call's: nothing waits for spe_extend_fetch)
-    map_reset(ix);
-    ix->map_ready = false;
+    if ((rc = ready_take(ix->extend_ready, nreads, n_in, "spn_map_begin", "the extended CIGARs")) != SPX_OK) return rc;
+    product_reset(ix, ix->map);
+    ix->map_ready.ok = false;
     if (nreads == 0) {
         ix->map.have = true;  // (the stats of an empty batch are zeros)
-        ix->map_ready = true;
-        ix->map_ready_n = ix->map_ready_reads = 0;
+        ready_publish(ix->map_ready, 0, 0);
         return SPX_OK;
     }
     // the reads' lengths in the characters the walk saw are the values spe_extend_begin reports
@@ -600,16 +561,14 @@ int spn_map_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const 
     SPX_HIP(hipMemcpyAsync(out_mappings, d_out, nreads * sizeof(spn_mapping), hipMemcpyDeviceToHost, st));
     // the one wait of the mapping's own: for the records and the entry count
     if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
-    if ((rc = map_collect(ix)) != SPX_OK) return rc;
+    if ((rc = product_collect(ix, ix->map, MAP_WORDS, MAP_WORDS - 1)) != SPX_OK) return rc;
     if ((rc = map_error_code(ix)) != SPX_OK) return rc;
     if (ix->map.error & 2) {
         set_error("internal: the bound of the mapping's entries did not hold");
         return SPX_E_FORMAT;
     }
-    ix->map_ready = true;
-    ix->map_ready_n = ix->map_acc[5];
-    ix->map_ready_reads = nreads;
-    *n_entries = ix->map_ready_n;
+    *n_entries = ix->map.acc[5];
+    ready_publish(ix->map_ready, *n_entries, nreads);
     return quiet.done(SPX_OK);
 }
 
@@ -618,24 +577,8 @@ int spn_map_fetch(spx_index* ix, uint64_t* out_op_offsets, uint32_t* out_ops) {
         set_error("index must be non-null");
         return SPX_E_ARG;
     }
-    std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (!ix->map_ready) {
-        set_error("spn_map_fetch without a successful spn_map_begin before it");
-        return SPX_E_ARG;
-    }
-    if (!out_op_offsets || (ix->map_ready_n && !out_ops)) {
-        set_error("out_op_offsets and out_ops must be non-null");
-        return SPX_E_ARG;
-    }
-    ix->map_ready = false;
-    if (ix->map_ready_reads == 0) {
-        out_op_offsets[0] = 0;
-        return SPX_OK;
-    }
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipMemcpy(out_op_offsets, ix->map_scr[spx_index::N_OOFFS].p, (ix->map_ready_reads + 1) * 8, hipMemcpyDeviceToHost));
-    if (ix->map_ready_n) SPX_HIP(hipMemcpy(out_ops, ix->map_scr[spx_index::N_OPS].p, ix->map_ready_n * 4, hipMemcpyDeviceToHost));
-    return SPX_OK;
+    return ready_fetch(ix, ix->map_ready, ix->map_scr[spx_index::N_OOFFS], ix->map_scr[spx_index::N_OPS], "spn_map_fetch", "spn_map_begin",
+                       out_op_offsets, out_ops);
 }
 
 }  // extern "C"

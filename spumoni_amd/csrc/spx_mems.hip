@@ -32,6 +32,9 @@ struct MemCounters {  // device; zeroed in front of every count
     unsigned long long values, matches, longest;
     unsigned long long error;  // bit 0: a read of 2^32 values or more, or decreasing offsets; bit 1: more values than total_values said
 };
+// (longest is a maximum, not a sum: every call resets before it enqueues and collects once, so product_collect's adding is
+// assigning)
+constexpr int MEM_WORDS = sizeof(MemCounters) / 8;
 struct MemArgs {
     const uint4* L;
     const uint64_t* P;
@@ -186,18 +189,12 @@ __global__ __launch_bounds__(256) void k_mems_write(MemArgs a) {
 
 uint64_t words_for(uint64_t total_values) { return total_values / 64 + 2; }  // (base need not be a multiple of 64)
 
-int ensure_events(spx_index* ix) {
-    for (auto& e : ix->ev_m)
-        if (!e) SPX_HIP(hipEventCreate(&e));
-    return SPX_OK;
-}
-
-// mark, force, scan and offsets on st: d_match_offsets complete, the bitmap and the ranks left in the scratch.  Takes ix->mu.
+// mark, force, scan and offsets on st: d_match_offsets complete, the bitmap and the ranks left in the scratch.  Opens the
+// product: the count is its step 0, and what follows belongs to no step (in the host form, a wait).  Takes ix->mu.
 int mems_enqueue_count(spx_index* ix, MemArgs& a, int value_bits, uint64_t total_values, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
     int rc;
-    if ((rc = ensure_events(ix)) != SPX_OK) return rc;
     a.nwords = words_for(total_values);
     if (a.nwords + 1 >= (1ull << 31)) {
         set_error("total_values is too large for one call (2^37 values)");
@@ -207,18 +204,14 @@ int mems_enqueue_count(spx_index* ix, MemArgs& a, int value_bits, uint64_t total
     size_t cub_bytes = 0;
     SPX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, PopcountIter(nullptr, Popcount()), (uint64_t*)nullptr, items, st));
     void* p = nullptr;
-    if ((rc = ix->mems_scr[spx_index::M_COUNTERS].reserve(sizeof(MemCounters), &p)) != SPX_OK) return rc;
-    a.c = (MemCounters*)p;
     if ((rc = ix->mems_scr[spx_index::M_BITS].reserve((a.nwords + 1) * 8, &p)) != SPX_OK) return rc;
     a.bits = (uint64_t*)p;
     if ((rc = ix->mems_scr[spx_index::M_PREFIX].reserve((a.nwords + 1) * 8, &p)) != SPX_OK) return rc;
     a.prefix = (uint64_t*)p;
     void* cub = nullptr;
     if ((rc = ix->mems_scr[spx_index::M_CUB].reserve(cub_bytes + 256, &cub)) != SPX_OK) return rc;
-    // the counters, the bitmap and the events are the index's: a call on another stream waits for the one before
-    if (ix->have_mems && ix->mems_stream != st) SPX_HIP(hipStreamWaitEvent(st, ix->ev_m[3], 0));
-    SPX_HIP(hipMemsetAsync(a.c, 0, sizeof(MemCounters), st));
-    SPX_HIP(hipEventRecord(ix->ev_m[0], st));
+    if ((rc = product_open(ix->mems, MEM_WORDS, st, 0, &p)) != SPX_OK) return rc;
+    a.c = (MemCounters*)p;
     const uint64_t lanes = (a.nwords + 1) * (value_bits == 16 ? 8 : 16);
     const unsigned mark_grid = (unsigned)std::min<uint64_t>((lanes + 255) / 256, 4096);
     const unsigned read_grid = (unsigned)std::min<uint64_t>((a.nreads + 256) / 256, 2048);
@@ -233,15 +226,15 @@ int mems_enqueue_count(spx_index* ix, MemArgs& a, int value_bits, uint64_t total
     SPX_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, PopcountIter(a.bits, Popcount()), a.prefix, items, st));
     k_mems_offsets<<<read_grid, 256, 0, st>>>(a);
     SPX_HIP(hipGetLastError());
-    SPX_HIP(hipEventRecord(ix->ev_m[1], st));
-    return SPX_OK;
+    return product_mark(ix->mems, -1, st);
 }
 
-// the records of rank < a.cap, behind mems_enqueue_count on the same stream.  Takes ix->mu.
+// the records of rank < a.cap, behind mems_enqueue_count on the same stream: step 1, and the product is closed.  Takes ix->mu.
 int mems_enqueue_write(spx_index* ix, const MemArgs& a, int value_bits, hipStream_t st) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventRecord(ix->ev_m[2], st));
+    int rc;
+    if ((rc = product_mark(ix->mems, 1, st)) != SPX_OK) return rc;
     const unsigned grid = (unsigned)std::min<uint64_t>((a.nwords + 255) / 256, 4096);
     const bool docs = a.D != nullptr;
     if (value_bits == 16) {
@@ -256,45 +249,22 @@ int mems_enqueue_write(spx_index* ix, const MemArgs& a, int value_bits, hipStrea
             k_mems_write<32, false><<<grid, 256, 0, st>>>(a);
     }
     SPX_HIP(hipGetLastError());
-    SPX_HIP(hipEventRecord(ix->ev_m[3], st));
-    ix->have_mems = true;
-    ix->mems_stream = st;
     ix->mems_capacity = a.cap;
-    return SPX_OK;
+    return product_close(ix->mems, st);
 }
 
-// Waits for the match kernels enqueued last and reads what they counted.  Takes ix->mu.
-int mems_collect(spx_index* ix) {
-    std::lock_guard<std::mutex> g(ix->mu);
-    SPX_HIP(hipSetDevice(ix->device));
-    SPX_HIP(hipEventSynchronize(ix->ev_m[3]));
-    MemCounters c;
-    SPX_HIP(hipMemcpy(&c, ix->mems_scr[spx_index::M_COUNTERS].p, sizeof c, hipMemcpyDeviceToHost));
-    float count_ms = 0, write_ms = 0;
-    SPX_HIP(hipEventElapsedTime(&count_ms, ix->ev_m[0], ix->ev_m[1]));
-    SPX_HIP(hipEventElapsedTime(&write_ms, ix->ev_m[2], ix->ev_m[3]));
-    ix->mems_acc[0] = c.values;
-    ix->mems_acc[1] = c.matches;
-    ix->mems_acc[2] = c.longest;
-    ix->mems_acc[3] = c.error;
-    ix->mems_ms = count_ms + write_ms;
-    ix->mems_pending = false;
-    return SPX_OK;
-}
 void mems_reset(spx_index* ix) {
+    product_reset(ix, ix->mems);
     std::lock_guard<std::mutex> g(ix->mu);
-    std::memset(ix->mems_acc, 0, sizeof ix->mems_acc);
-    ix->mems_ms = 0;
     ix->mems_capacity = 0;
-    ix->mems_pending = false;
-    ix->mems_ready = false;
+    ix->mems_ready.ok = false;
 }
 int mems_error_code(const spx_index* ix) {
-    if (ix->mems_acc[3] & 1) {
+    if (ix->mems.error & 1) {
         set_error("a read has 2^32 values or more (or its offsets decrease): the matches take reads below that");
         return SPX_E_FORMAT;
     }
-    if (ix->mems_acc[3] & 2) {
+    if (ix->mems.error & 2) {
         set_error("the batch holds more values than total_values said: the output is undefined");
         return SPX_E_FORMAT;
     }
@@ -303,12 +273,7 @@ int mems_error_code(const spx_index* ix) {
 
 }  // namespace
 
-void release_mems(spx_index* ix) {
-    for (auto& sc : ix->mems_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    for (auto& e : ix->ev_m)
-        if (e) (void)hipEventDestroy(e);
-}
+void release_mems(spx_index* ix) { release(ix->mems_scr, spx_index::M_COUNT, &ix->mems); }
 
 }  // namespace spx
 
@@ -365,9 +330,7 @@ int spm_mems_device(spx_index* ix, const void* d_lengths, int value_bits, const 
     a.out_docs = d_out_docs;
     int rc;
     if ((rc = mems_enqueue_count(ix, a, value_bits, total_values, st)) != SPX_OK) return rc;
-    if ((rc = mems_enqueue_write(ix, a, value_bits, st)) != SPX_OK) return rc;
-    ix->mems_pending = true;
-    return SPX_OK;
+    return mems_enqueue_write(ix, a, value_bits, st);
 }
 
 int spm_last_mems_stats(spx_index* ix, spm_mems_stats* out) {
@@ -375,15 +338,16 @@ int spm_last_mems_stats(spx_index* ix, spm_mems_stats* out) {
         set_error("null argument");
         return SPX_E_ARG;
     }
-    if (ix->mems_pending) {
-        const int rc = mems_collect(ix);
+    const spx_index::Product& p = ix->mems;
+    if (p.pending) {
+        const int rc = product_collect(ix, ix->mems, MEM_WORDS, MEM_WORDS - 1);
         if (rc != SPX_OK) return rc;
     }
-    out->values = ix->mems_acc[0];
-    out->matches = ix->mems_acc[1];
-    out->written = std::min(ix->mems_acc[1], ix->mems_capacity);
-    out->longest = ix->mems_acc[2];
-    out->kernel_ms = ix->mems_ms;
+    out->values = p.acc[0];
+    out->matches = p.acc[1];
+    out->written = std::min(p.acc[1], ix->mems_capacity);
+    out->longest = p.acc[2];
+    out->kernel_ms = p.step_ms[0] + p.step_ms[1];  // (count and write: not what lies between them)
     return mems_error_code(ix);
 }
 
@@ -398,34 +362,16 @@ int spm_mems_begin(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, const
         set_error("index, match_offsets and n_matches must be non-null");
         return SPX_E_ARG;
     }
-    if (min_length == 0) {
-        set_error("min_length must be at least 1: a position of length 0 matches nothing");
-        return SPX_E_ARG;
-    }
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
-    if (!ix->has_samples || !ix->text) {
-        set_error("the matches need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)");
-        return SPX_E_ARG;
-    }
-    if (want_docs && !ix->has_docs) {
-        set_error("document ids requested but the index has no document array");
-        return SPX_E_ARG;
-    }
-    if (nreads && (!seqs || !offsets)) {
-        set_error("seqs and offsets must be non-null");
-        return SPX_E_ARG;
-    }
+    const int rc = check_batch(ix, "the matches", BATCH_MIN_LENGTH | BATCH_TEXT, min_length, digest_kind, want_docs,
+                               nreads && (!seqs || !offsets) ? "seqs and offsets must be non-null" : nullptr, offsets, nreads);
+    if (rc != SPX_OK) return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     mems_reset(ix);
     *n_matches = 0;
     match_offsets[0] = 0;
     if (nreads == 0) {
-        ix->mems_ready = true;
-        ix->mems_ready_n = 0;
+        ready_publish(ix->mems_ready, 0, 0);
         ix->mems_ready_docs = want_docs != 0;
         return SPX_OK;
     }
@@ -490,19 +436,19 @@ int mems_begin_staged(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, co
         a.out_docs = (uint32_t*)d_out_docs;
         a.cap = n;
         if ((r = mems_enqueue_write(ix, a, v.value_bits, st)) != SPX_OK) return r;
-        ix->mems_pending = true;
         if (then && (r = then(MemsOnDevice{v.reads, v.offs, (const uint64_t*)d_moffs, d_out, (const uint32_t*)d_out_docs, nreads, n, st})) != SPX_OK)
             return r;
-        if ((r = mems_collect(ix)) != SPX_OK) return r;
+        if ((r = product_collect(ix, ix->mems, MEM_WORDS, MEM_WORDS - 1)) != SPX_OK) return r;
         if (then && (r = ctx_wait(ix, st)) != SPX_OK) return r;
         return mems_error_code(ix);
     };
     QuietOnError quiet(st);  // (a failed call leaves nothing reading seqs / offsets or writing the outputs)
     if ((rc = stage_run(ix, job, plan)) != SPX_OK) return rc;
     *n_matches = n;
-    ix->mems_ready = true;
-    ix->mems_ready_n = n;
-    ix->mems_ready_docs = want_docs != 0;
+    if (!then) {  // (with `then` the records are its caller's: nothing waits for spm_mems_fetch)
+        ready_publish(ix->mems_ready, n, nreads);
+        ix->mems_ready_docs = want_docs != 0;
+    }
     return quiet.done(SPX_OK);
 }
 
@@ -516,11 +462,11 @@ int spm_mems_fetch(spx_index* ix, spm_match* out, uint32_t* out_docs) {
         return SPX_E_ARG;
     }
     std::lock_guard<std::mutex> hg(ix->host_mu);
-    if (!ix->mems_ready) {
+    if (!ix->mems_ready.ok) {
         set_error("spm_mems_fetch without a successful spm_mems_begin");
         return SPX_E_ARG;
     }
-    const uint64_t n = ix->mems_ready_n;
+    const uint64_t n = ix->mems_ready.n;
     if (n && (!out || (ix->mems_ready_docs && !out_docs))) {
         set_error("out (and, when ids were asked for, out_docs) must be non-null");
         return SPX_E_ARG;
@@ -537,7 +483,7 @@ int spm_mems_fetch(spx_index* ix, spm_match* out, uint32_t* out_docs) {
         if ((rc = ctx_wait(ix, st)) != SPX_OK) return rc;
         quiet.done(SPX_OK);
     }
-    ix->mems_ready = false;
+    ix->mems_ready.ok = false;
     return SPX_OK;
 }
 

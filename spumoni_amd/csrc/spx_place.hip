@@ -382,11 +382,7 @@ int check_params(const spx_index* ix, uint64_t min_seed, uint32_t mismatch_penal
 
 }  // namespace
 
-void release_place(spx_index* ix) {
-    for (auto& sc : ix->place_scr)
-        if (sc.p) (void)hipFree(sc.p);
-    product_release(ix->place);
-}
+void release_place(spx_index* ix) { release(ix->place_scr, 2, &ix->place); }
 
 }  // namespace spx
 
@@ -466,22 +462,9 @@ int spp_place_batch(spx_index* ix, int digest_kind, uint32_t k, uint32_t w, cons
     }
     int rc = check_params(ix, min_seed, mismatch_penalty, x_drop);
     if (rc != SPX_OK) return rc;
-    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
-        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
-        return SPX_E_ARG;
-    }
-    if (!ix->has_samples || !ix->text) {
-        set_error("the placements need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)");
-        return SPX_E_ARG;
-    }
-    if (want_docs && !ix->has_docs) {
-        set_error("document ids requested but the index has no document array");
-        return SPX_E_ARG;
-    }
-    if (nreads && (!seqs || !offsets || !out)) {
-        set_error("seqs, offsets and out must be non-null");
-        return SPX_E_ARG;
-    }
+    if ((rc = check_batch(ix, "the placements", BATCH_TEXT, 0, digest_kind, want_docs,
+                          nreads && (!seqs || !offsets || !out) ? "seqs, offsets and out must be non-null" : nullptr, offsets, nreads)) != SPX_OK)
+        return rc;
     std::lock_guard<std::mutex> hg(ix->host_mu);
     SPX_HIP(hipSetDevice(ix->device));
     product_reset(ix, ix->place);

@@ -1,5 +1,7 @@
 // spx_stage.hip -- the staged walk under the products over a batch of reads in host memory (spv_assign_batch,
-// spm_mems_begin, spp_place_batch; spx_internal.h has the interface), and the counters of a product's kernels.
+// spm_mems_begin, spp_place_batch; spx_internal.h has the interface), and what every product does alike on the host: the
+// counters, events and step times of its kernels (Product), the records that wait for its _fetch (Ready), the argument
+// checks of the host forms and the release of its scratch.
 //
 // What the products share is here once: the checks of the offsets, the cuts, the width of the values, the buffer sets, the
 // rebased offsets and the zeroed tail of a piece, the four-way dispatch of digestion and walk, the digested offsets on
@@ -147,29 +149,72 @@ int stage_run(spx_index* ix, const StageJob& job, const StagePlan& plan) {
 }
 
 void release_stage(spx_index* ix) {
-    for (auto& sc : ix->stage_scr)
-        if (sc.p) (void)hipFree(sc.p);
+    release(ix->stage_scr, spx_index::G_COUNT, nullptr);
     for (auto& st : ix->stage_s)
         if (st) (void)hipStreamDestroy(st);
 }
 
-int product_collect(spx_index* ix, spx_index::Product& p, int words, int nacc) {
+int product_open(spx_index::Product& p, size_t words, hipStream_t st, int step, void** c) {
+    if (!p.ev0) SPX_HIP(hipEventCreate(&p.ev0));
+    if (!p.ev1) SPX_HIP(hipEventCreate(&p.ev1));
+    int rc;
+    if ((rc = p.counters.reserve(words * 8, c)) != SPX_OK) return rc;
+    if (p.have && p.stream != st) SPX_HIP(hipStreamWaitEvent(st, p.ev1, 0));
+    SPX_HIP(hipMemsetAsync(*c, 0, words * 8, st));
+    SPX_HIP(hipEventRecord(p.ev0, st));
+    p.label0 = step < spx_index::Product::STEPS ? step : -1;  // (product_mark refuses such a label; here it is a constant)
+    p.nmarks = 0;
+    return SPX_OK;
+}
+int product_mark(spx_index::Product& p, int step, hipStream_t st) {
+    if (p.nmarks == spx_index::Product::MARKS || step >= spx_index::Product::STEPS) {
+        set_error("internal: more marks, or a later step, than a product holds");
+        return SPX_E_ARG;
+    }
+    hipEvent_t& e = p.ev_mark[p.nmarks];
+    if (!e) SPX_HIP(hipEventCreate(&e));
+    SPX_HIP(hipEventRecord(e, st));
+    p.label[p.nmarks++] = step;
+    return SPX_OK;
+}
+int product_close(spx_index::Product& p, hipStream_t st) {
+    SPX_HIP(hipEventRecord(p.ev1, st));
+    p.have = p.pending = true;
+    p.stream = st;
+    return SPX_OK;
+}
+int product_collect(spx_index* ix, spx_index::Product& p, int words, int nacc, int error_word) {
     std::lock_guard<std::mutex> g(ix->mu);
     SPX_HIP(hipSetDevice(ix->device));
     SPX_HIP(hipEventSynchronize(p.ev1));
-    unsigned long long c[16];
+    unsigned long long c[spx_index::Product::WORDS];
     SPX_HIP(hipMemcpy(c, p.counters.p, (size_t)words * 8, hipMemcpyDeviceToHost));
+    if (error_word < 0) error_word = words - 1;
+    for (int i = 0; i < nacc; ++i)
+        if (i != error_word) p.acc[i] += c[i];
+    p.error |= c[error_word];
     float ms = 0;
     SPX_HIP(hipEventElapsedTime(&ms, p.ev0, p.ev1));
-    for (int i = 0; i < nacc; ++i) p.acc[i] += c[i];
     p.ms += ms;
-    p.error |= c[words - 1];
+    // the boundaries ev0, the marks, ev1: what lies between two of them is the step's that the first one names
+    hipEvent_t from = p.ev0;
+    int step = p.label0;
+    for (int i = 0; i <= p.nmarks; ++i) {
+        hipEvent_t to = i < p.nmarks ? p.ev_mark[i] : p.ev1;
+        if (step >= 0) {
+            SPX_HIP(hipEventElapsedTime(&ms, from, to));
+            p.step_ms[step] += ms;
+        }
+        from = to;
+        step = i < p.nmarks ? p.label[i] : -1;
+    }
     p.pending = false;
     return SPX_OK;
 }
 void product_reset(spx_index* ix, spx_index::Product& p) {
     std::lock_guard<std::mutex> g(ix->mu);
     std::memset(p.acc, 0, sizeof p.acc);
+    std::memset(p.step_ms, 0, sizeof p.step_ms);
     p.ms = 0;
     p.error = 0;
     p.pending = false;
@@ -178,6 +223,80 @@ void product_release(spx_index::Product& p) {
     if (p.counters.p) (void)hipFree(p.counters.p);
     if (p.ev0) (void)hipEventDestroy(p.ev0);
     if (p.ev1) (void)hipEventDestroy(p.ev1);
+    for (hipEvent_t e : p.ev_mark)
+        if (e) (void)hipEventDestroy(e);
+}
+void release(spx_index::Scratch* scr, int n, spx_index::Product* p) {
+    for (int i = 0; i < n; ++i)
+        if (scr[i].p) (void)hipFree(scr[i].p);
+    if (p) product_release(*p);
+}
+
+int ready_take(spx_index::Ready& r, uint64_t reads, uint64_t n, const char* who, const char* whose) {
+    // (another host thread on this handle between the two locks would have taken the entries or replaced them)
+    if (!r.ok || r.reads != reads || r.n != n) {
+        set_error("%s: another call on this index took %s: calls on one handle must not overlap", who, whose);
+        return SPX_E_ARG;
+    }
+    r.ok = false;
+    return SPX_OK;
+}
+int ready_fetch(spx_index* ix, spx_index::Ready& r, const spx_index::Scratch& op_offsets, const spx_index::Scratch& ops,
+                const char* fetch_name, const char* begin_name, uint64_t* out_op_offsets, uint32_t* out_ops) {
+    std::lock_guard<std::mutex> hg(ix->host_mu);
+    if (!r.ok) {
+        set_error("%s without a successful %s before it", fetch_name, begin_name);
+        return SPX_E_ARG;
+    }
+    if (!out_op_offsets || (r.n && !out_ops)) {
+        set_error("out_op_offsets and out_ops must be non-null");
+        return SPX_E_ARG;
+    }
+    r.ok = false;
+    if (r.reads == 0) {
+        out_op_offsets[0] = 0;
+        return SPX_OK;
+    }
+    SPX_HIP(hipSetDevice(ix->device));
+    SPX_HIP(hipMemcpy(out_op_offsets, op_offsets.p, (r.reads + 1) * 8, hipMemcpyDeviceToHost));
+    if (r.n) SPX_HIP(hipMemcpy(out_ops, ops.p, r.n * 4, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int check_digest_kind(int digest_kind) {
+    if (digest_kind != 0 && digest_kind != SPX_DIGEST_PROMOTED && digest_kind != SPX_DIGEST_DNA) {
+        set_error("digest_kind must be 0, SPX_DIGEST_PROMOTED or SPX_DIGEST_DNA");
+        return SPX_E_ARG;
+    }
+    return SPX_OK;
+}
+int check_batch(const spx_index* ix, const char* what, int flags, uint64_t min_length, int digest_kind, int want_docs,
+                const char* null_pointers, const uint64_t* offsets, uint64_t nreads) {
+    constexpr uint64_t PIECE_CHARS = 32ull << 20, PIECE_READS = 4ull << 20;
+    if ((flags & BATCH_MIN_LENGTH) && min_length == 0) {
+        set_error("min_length must be at least 1: a position of length 0 matches nothing");
+        return SPX_E_ARG;
+    }
+    int rc;
+    if ((rc = check_digest_kind(digest_kind)) != SPX_OK) return rc;
+    if ((flags & BATCH_TEXT) && (!ix->has_samples || !ix->text)) {
+        set_error("%s need an index built with SA samples and the text (spx_index_set_text / spx_index_rebuild_text)", what);
+        return SPX_E_ARG;
+    }
+    if (want_docs && !ix->has_docs) {
+        set_error("document ids requested but the index has no document array");
+        return SPX_E_ARG;
+    }
+    if (null_pointers) {
+        set_error("%s", null_pointers);
+        return SPX_E_ARG;
+    }
+    if ((flags & BATCH_ONE_PIECE) &&
+        (nreads > PIECE_READS || (nreads && offsets[nreads] >= offsets[0] && offsets[nreads] - offsets[0] > PIECE_CHARS))) {
+        set_error("one piece per call: at most 32 Mi characters and 4 Mi reads");
+        return SPX_E_ARG;
+    }
+    return SPX_OK;
 }
 
 }  // namespace spx
