@@ -37,8 +37,8 @@
  *   - THE CONTRACT is the coverage's: fewer than 2^32 mapped reads between two resets.
  * Everything is a sum: the same input gives the same bytes, in any order of adds.
  *
- * Limits: indel alleles are not called, del and ins are evidence only; no genotypes or qualities; no consensus; one count
- * for both strands; one device; no digested indexes.
+ * Limits: indel alleles are not called, del and ins are evidence only; no genotypes or qualities; the sequence the
+ * counts imply is spumoni_consensus.h's product; one count for both strands; one device; no digested indexes.
  *
  * Conventions: those of spumoni_gpu.h (0 or a negative SPX_E* code, message in spx_last_error(), NO CPU fallback).
  */

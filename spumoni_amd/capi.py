@@ -199,6 +199,7 @@ class Index:
         n, r = C.c_uint64(), C.c_uint64()
         _check(lib().spx_index_stats(self._h, C.byref(n), C.byref(r)))
         self.n, self.r = n.value, r.value
+        self._n_seqs = 0  # of the sequence table set through this object (or the one it was cloned from)
 
     # -- construction -----------------------------------------------------
     @classmethod
@@ -265,7 +266,9 @@ class Index:
         h = lib().spx_index_clone(self._h, device)
         if not h:
             raise SpxError(lib().spx_last_error().decode())
-        return Index(h, device)
+        out = Index(h, device)
+        out._n_seqs = self._n_seqs  # (the table goes with the clone)
+        return out
 
     def describe(self) -> dict:
         import json
@@ -874,6 +877,7 @@ class Index:
         """The sequence table (map.read_seq_table's lengths and strands): copied to the device and held in the handle."""
         lengths = np.ascontiguousarray(seq_lengths, dtype=np.uint64)
         _check(_spn().spn_set_sequences(self._h, _np_ptr(lengths), lengths.size, int(strands)))
+        self._n_seqs = int(lengths.size)
 
     def map_device(self, d_alignments, d_op_offsets, d_ops, d_read_offsets, op_capacity=None, in_entries=None, d_out=None,
                    d_out_op_offsets=None, d_out_ops=None, stream=None):
@@ -1132,6 +1136,50 @@ class Index:
         s = SplCallStats()
         _check(_spl().spl_last_call_stats(self._h, C.byref(s)))
         out = {f[0]: getattr(s, f[0]) for f in SplCallStats._fields_ if f[0] != "reserved"}
+        out["step_ms"] = list(s.step_ms)
+        return out
+
+    # -- consensus (include/spumoni_consensus.h) ----------------------------------------------
+    def consensus_device(self, d_depth, d_alt, d_ins, d_del, min_depth=2, min_alt=2, min_permille=500, mask=ord("N"), line_width=60,
+                         body_capacity=0, d_records=None, d_body=None, d_count=None, stream=None):
+        """(d_records int64 (n_seqs, 6), a view of consensus.SEQ_DTYPE; d_body uint8[body_capacity] or None; d_count int64[1]):
+        the consensus of the arrays (consensus.py).  n_seqs is d_records' when it is given, else the table's as set through
+        set_sequences on this object."""
+        import torch
+
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if d_records is None:
+            d_records = torch.empty((self._n_seqs, 6), dtype=torch.int64, device=d_depth.device)
+        if d_body is None and body_capacity:
+            d_body = torch.empty(int(body_capacity), dtype=torch.uint8, device=d_depth.device)
+        if d_count is None:
+            d_count = torch.empty(1, dtype=torch.int64, device=d_depth.device)
+        p = _sps_params(min_depth, min_alt, min_permille, mask, line_width)
+        _check(_sps().sps_consensus_device(self._h, _t_ptr(d_depth), _t_ptr(d_alt), _t_ptr(d_ins), _t_ptr(d_del), C.byref(p),
+                                           int(body_capacity), _t_ptr(d_records), _t_ptr(d_body), _t_ptr(d_count),
+                                           C.c_void_p(st.cuda_stream)))
+        return d_records, d_body, d_count
+
+    def consensus(self, min_depth: int = 2, min_alt: int = 2, min_permille: int = 500, mask=ord("N"), line_width: int = 60):
+        """sps_consensus_begin + _fetch on the handle's arrays of call_reset / call_add_host: (consensus.SEQ_DTYPE[n_seqs],
+        body uint8[])."""
+        from .consensus import SEQ_DTYPE
+
+        L = _sps()
+        n = C.c_uint64(0)
+        p = _sps_params(min_depth, min_alt, min_permille, mask, line_width)
+        _check(L.sps_consensus_begin(self._h, C.byref(p), C.byref(n)))
+        records = np.zeros(max(self._n_seqs, 1), dtype=SEQ_DTYPE)
+        body = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(L.sps_consensus_fetch(self._h, _np_ptr(records), _np_ptr(body)))
+        return records[:self._n_seqs], body[:n.value]
+
+    def consensus_stats(self) -> dict:
+        """Of the most recent consensus: the positions and how they were decided, the insertion sites, the letters and the
+        bytes of the body, the overflow flag and the time of the count, the scans and the write."""
+        s = SpsConsensusStats()
+        _check(_sps().sps_last_consensus_stats(self._h, C.byref(s)))
+        out = {f[0]: getattr(s, f[0]) for f in SpsConsensusStats._fields_}
         out["step_ms"] = list(s.step_ms)
         return out
 
@@ -1490,6 +1538,50 @@ def _spl() -> C.CDLL:
         L.spl_pileup_counts.argtypes = [vp, u64, u64, vp, vp, vp, vp]
         L.spl_last_call_stats.argtypes = [vp, C.POINTER(SplCallStats)]
         _SPL_READY = True
+    return L
+
+
+# ---- the consensus (include/spumoni_consensus.h) -------------------------------------------------------------------
+CONSENSUS_EXPORTS = ["sps_consensus_device", "sps_consensus_begin", "sps_consensus_fetch", "sps_last_consensus_stats"]
+_SPS_READY = False
+
+
+class SpsParams(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_permille", C.c_uint32), ("line_width", C.c_uint32),
+                ("mask", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class SpsConsensusStats(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("kept", C.c_uint64), ("substituted", C.c_uint64), ("deleted", C.c_uint64),
+                ("masked", C.c_uint64), ("ins_sites", C.c_uint64), ("letters", C.c_uint64), ("bytes", C.c_uint64),
+                ("overflow", C.c_uint32), ("step_ms", C.c_float * 3)]
+
+
+def _sps_params(min_depth, min_alt, min_permille, mask, line_width) -> SpsParams:
+    """The parameters as the library takes them: the ranges are the library's to check, the fields' widths are checked here."""
+    if isinstance(mask, (bytes, bytearray)):
+        if len(mask) != 1:
+            raise ValueError("mask must be one byte")
+        mask = mask[0]
+    vals = [int(min_depth), int(min_alt), int(min_permille), int(line_width)]
+    if not (0 <= int(mask) <= 255) or any(v < 0 or v > 0xFFFFFFFF for v in vals):
+        raise ValueError("min_depth, min_alt, min_permille and line_width must fit 32 bits, mask one byte")
+    return SpsParams(vals[0], vals[1], vals[2], vals[3], int(mask))
+
+
+def _sps() -> C.CDLL:
+    """The library with the sps_* argtypes set (on first use)."""
+    global _SPS_READY
+    L = _spl()
+    if not hasattr(L, "sps_consensus_begin"):
+        raise SpxError(f"{LIB_PATH} has no consensus kernels (sps_consensus_begin): there is no CPU fallback")
+    if not _SPS_READY:
+        vp, u64 = C.c_void_p, C.c_uint64
+        L.sps_consensus_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SpsParams), u64, vp, vp, vp, vp]
+        L.sps_consensus_begin.argtypes = [vp, C.POINTER(SpsParams), C.POINTER(u64)]
+        L.sps_consensus_fetch.argtypes = [vp, vp, vp]
+        L.sps_last_consensus_stats.argtypes = [vp, C.POINTER(SpsConsensusStats)]
+        _SPS_READY = True
     return L
 
 

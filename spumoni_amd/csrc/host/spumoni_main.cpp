@@ -384,6 +384,7 @@ int extend_main(int argc, char** argv);  // extend_main.cpp
 int map_main(int argc, char** argv);  // map_main.cpp
 int cover_main(int argc, char** argv);  // cover_main.cpp
 int call_main(int argc, char** argv);  // call_main.cpp
+int consensus_main(int argc, char** argv);  // consensus_main.cpp
 
 static int spumoni_usage() {
     std::fprintf(stderr, "SPUMONI has different sub-commands to run which can used as follows:\n");
@@ -400,7 +401,8 @@ static int spumoni_usage() {
     std::fprintf(stderr, "\textend\treports the CIGAR of `cigar` taken to the read's ends: both ends extended in a band, the rest soft-clipped.\n");
     std::fprintf(stderr, "\tmap\tmaps each read: the alignment of `extend` by sequence name, strand and position in the sequence, as PAF.\n");
     std::fprintf(stderr, "\tcover\tmaps each read as `map` does and reports per sequence how much of it the reads cover and how deep.\n");
-    std::fprintf(stderr, "\tcall\tmaps each read as `map` does and reports where the reads support a letter other than the reference's, as VCF.\n\n");
+    std::fprintf(stderr, "\tcall\tmaps each read as `map` does and reports where the reads support a letter other than the reference's, as VCF.\n");
+    std::fprintf(stderr, "\tconsensus\tmaps each read as `map` does and writes the sequences the reads imply: substitutions and deletions applied, low depth masked, as FASTA.\n\n");
     return 1;
 }
 
@@ -421,6 +423,7 @@ int main(int argc, char** argv) {
         if (std::strcmp(argv[1], "map") == 0) return map_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "cover") == 0) return cover_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "call") == 0) return call_main(argc - 1, argv + 1);
+        if (std::strcmp(argv[1], "consensus") == 0) return consensus_main(argc - 1, argv + 1);
         if (std::strcmp(argv[1], "run") == 0) {
             const int rc = run_main(argc - 1, argv + 1);
             if (std::getenv("SPX_FREE_TRACE")) std::fprintf(stderr, "[spumoni] main returns %d\n", rc);

@@ -186,6 +186,7 @@ void spx_index_free(spx_index* ix) {
     release_map(ix);
     release_cover(ix);
     release_call(ix);
+    release_consensus(ix);
     if (ix->ev_dig) (void)hipEventDestroy(ix->ev_dig);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);

@@ -412,6 +412,8 @@ void release_call(spx_index* ix) {
 }
 int clone_call(spx_index* src, spx_index* ix) { return src->call.G ? spl_call_reset(ix) : SPX_OK; }
 void call_table_changed(spx_index* ix) { acc_table_changed(ix->call); }
+int call_arrays_ready(spx_index* ix, const char* who) { return call_need_arrays(ix, who); }
+int call_finish_arrays(spx_index* ix) { return call_finish_host(ix); }
 
 }  // namespace spx
 

@@ -381,6 +381,15 @@ struct spx_index {
     GenomeAcc call;
     hipStream_t call_copy_s = nullptr;
     hipEvent_t call_copy_ev = nullptr;
+    // consensus (spx_consensus.hip): the emitted byte of every position, the tiles' letter counts and their offsets, each
+    // sequence's (letters, bytes) and their running sums, the scans' space (under mu), then sps_consensus_begin's records
+    // and body (under host_mu), which wait for sps_consensus_fetch: cons_seqs records, cons_bytes bytes.  cons_G: the
+    // positions of the last call
+    enum { CS_EMIT, CS_TCNT, CS_TOFFS, CS_PAIRS, CS_STARTS, CS_CUB, CS_CUB2, CS_RECORDS, CS_BODY, CS_NOUT, CS_COUNT };
+    Scratch cons_scr[CS_COUNT];
+    Product cons;  // acc: letters, substituted, deleted, masked, insertion sites, bytes; steps: count, scans, write
+    uint64_t cons_G = 0, cons_seqs = 0, cons_bytes = 0;
+    bool cons_ready = false;
     // spx_query_text_begin -> spx_query_text_fetch: the streams' sizes and where they wait on the device
     uint64_t text_bytes[3] = {0, 0, 0};
     uint64_t text_nreads = 0;
@@ -559,6 +568,14 @@ int cover_finish_host(spx_index* ix);                   // ... and depth is brou
 void release_call(spx_index* ix);
 void call_table_changed(spx_index* ix);
 int clone_call(spx_index* src, spx_index* ix);
+// ... and for a product that goes on from the pileup's arrays (spx_consensus.hip; the caller holds host_mu): they and the
+// coverage's are there, named as `who`'s refusal; and del is brought up to date
+int call_arrays_ready(spx_index* ix, const char* who);
+int call_finish_arrays(spx_index* ix);
+// spx_consensus.hip: frees what the consensus holds of the device; and what spn_set_sequences does to it (the caller holds
+// host_mu and mu): the records and the body that wait for the fetch belong to the table that goes
+void release_consensus(spx_index* ix);
+void consensus_table_changed(spx_index* ix);
 // spx_mems.hip: what spm_mems_begin does behind its argument checks -- the staged walk in MS mode with exactly one piece,
 // count -> host wait -> records at their exact size -> k_mems_write -- for a product that goes on from the records on the
 // device.  `then` (may be empty) is called with the write kernels enqueued and enqueues its own work behind them on

@@ -433,6 +433,7 @@ int spn_set_sequences(spx_index* ix, const uint64_t* seq_lengths, uint64_t n_seq
     ix->map_ready.ok = false;
     cover_table_changed(ix);
     call_table_changed(ix);
+    consensus_table_changed(ix);
     return SPX_OK;
 }
 
