@@ -55,10 +55,7 @@ int align_main(int argc, char** argv) {
     parse_read_options(argc, argv, o, spumoni_align_usage, true, m.shorts().c_str(), m.longs(),
                        [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni align`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    o.ms = true;
+    imply_ms(o, "align");
     validate_read_options(o);
     m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";

@@ -6,7 +6,6 @@
 // lines are call_vcf.hpp's; the file is written when everything has been fetched, so a run that fails leaves none.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -50,88 +49,38 @@ int call_main(int argc, char** argv) {
     if (argc == 1) return spumoni_call_usage();
     ReadOptions o;
     MapOptions m(MapOptions::EXTEND);
-    unsigned long long min_depth = 2, min_alt = 2, min_permille = 500;
-    parse_read_options(argc, argv, o, spumoni_call_usage, true, m.shorts("D:A:Q:").c_str(),
-                       m.longs({{"min-depth", required_argument, NULL, 'D'},
-                                {"min-alt", required_argument, NULL, 'A'},
-                                {"min-permille", required_argument, NULL, 'Q'}}),
+    CallThresholds t;
+    parse_read_options(argc, argv, o, spumoni_call_usage, true, m.shorts(t.shorts().c_str()).c_str(), m.longs(t.longs()),
                        [&](int c, const char* arg) {
-                           if (!m.set(o, c, arg)) (c == 'D' ? min_depth : c == 'A' ? min_alt : min_permille) = count_argument(arg);
+                           if (!m.set(o, c, arg)) t.set(c, arg);
                        });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni call`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    if (o.use_promotions || o.use_dna_letters)
-        fatal_warning("-m / -a cannot be used with `spumoni call`: digested coordinates cannot be turned back into bases. "
-                      "Map against an index built with -n -s.");
-    if (o.min_digest)
-        fatal_warning("`spumoni call` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
-    o.ms = true;
+    imply_ms(o, "call");
+    require_bases(o, "call");
     validate_read_options(o);
     m.validate(o);
-    if (min_depth < 1 || min_depth > 4294967295ull) fatal_warning("the smallest depth (-D) must be between 1 and 4294967295.");
-    if (min_alt < 1 || min_alt > 4294967295ull) fatal_warning("the fewest reads with the called letter (-A) must be between 1 and 4294967295.");
-    if (min_permille > 1000) fatal_warning("the smallest share (-Q) must be between 0 and 1000 thousandths.");
-    o.ref_file += ".fa";
-    const std::string table_path = o.ref_file + ".seqs";
-    if (!is_file(table_path))
-        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", table_path.c_str());
-    const SeqTable table = read_seq_table(table_path);
-    const std::vector<void*> entry =
-        device_entry_points("call", {"spl_call_add_batch", "spn_set_sequences", "spl_call_reset", "spl_calls_begin", "spl_calls_fetch",
-                                     "spd_cover_depth"}, "the pileup kernels");
-    auto add_batch = reinterpret_cast<decltype(&spl_call_add_batch)>(entry[0]);
-    auto set_sequences = reinterpret_cast<decltype(&spn_set_sequences)>(entry[1]);
-    auto reset = reinterpret_cast<decltype(&spl_call_reset)>(entry[2]);
-    auto calls_begin = reinterpret_cast<decltype(&spl_calls_begin)>(entry[3]);
-    auto calls_fetch = reinterpret_cast<decltype(&spl_calls_fetch)>(entry[4]);
-    auto cover_depth = reinterpret_cast<decltype(&spd_cover_depth)>(entry[5]);
-    ReadRun run;
-    open_read_run(o, 8u << 20, run);
-    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spl_call_add_batch)
-    if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
-        fatal_error("%s: %s", table_path.c_str(), spx_last_error());
-    if (reset(run.ix) != SPX_OK) fatal_error("%s", spx_last_error());
-    const uint64_t min_length = m.min_length(o);
-    const spc_params params = m.chain();
-    const spa_params fill = m.fill();
-    const spe_params ends = m.ends();
-    std::fprintf(stderr, "[call] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); %s; a call needs depth %llu, %llu reads and "
-                 "%llu thousandths of the depth\n",
-                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
-                 m.describe(min_length).c_str(), min_depth, min_alt, min_permille);
+    t.validate("the fewest reads with the called letter");
+    TableRun run;
+    open_table_run(o, m, "call", {"spl_call_add_batch", "spn_set_sequences", "spl_call_reset", "spl_calls_begin", "spl_calls_fetch",
+                                  "spd_cover_depth"}, "the pileup kernels", "spl_call_reset", run);
+    const SeqTable& table = run.table;
+    std::fprintf(stderr, "%s; a call needs depth %llu, %llu reads and %llu thousandths of the depth\n", run.loaded.c_str(), t.min_depth,
+                 t.min_alt, t.min_permille);
 
-    LinesFile none;  // (nothing is written per read)
-    none.keep_partial = false;
-    uint64_t num_reads = 0, num_mapped = 0;
-    std::vector<spn_mapping> maps;
-    scan_reads(
-        run, none,
-        [&](ReadBatch& b) {
-            maps.resize(b.take + 1);
-            for_each_piece(b, [&](size_t q0, size_t q1) {
-                if (add_batch(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
-                              o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0) != SPX_OK)
-                    fatal_error("%s", spx_last_error());
-                // (without digestion a read's values are its characters)
-                for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
-            });
-        },
-        [&](const ReadBatch&, size_t i) {
-            num_reads++;
-            num_mapped += maps[i].seq != SPN_UNMAPPED;
-        });
+    const ReadCounts counts = accumulate_reads(run, o, m, run.entry<decltype(&spl_call_add_batch)>("spl_call_add_batch"));
     // everything that can fail on the device comes before the file
     uint64_t n = 0;
-    if (calls_begin(run.ix, (uint32_t)min_depth, (uint32_t)min_alt, (uint32_t)min_permille, &n) != SPX_OK) fatal_error("%s", spx_last_error());
+    if (run.entry<decltype(&spl_calls_begin)>("spl_calls_begin")(run.ix, (uint32_t)t.min_depth, (uint32_t)t.min_alt,
+                                                                 (uint32_t)t.min_permille, &n) != SPX_OK)
+        fatal_error("%s", spx_last_error());
     std::vector<spl_call> calls(n + 1);
-    if (calls_fetch(run.ix, calls.data()) != SPX_OK) fatal_error("%s", spx_last_error());
+    if (run.entry<decltype(&spl_calls_fetch)>("spl_calls_fetch")(run.ix, calls.data()) != SPX_OK) fatal_error("%s", spx_last_error());
     calls.resize(n);
     // ref_count is depth - mism: the mismatch counts of the calls' bases, from slices of 16 Mi positions that hold a call
     std::vector<uint64_t> starts(table.lengths.size() + 1, 0);
     for (size_t s = 0; s < table.lengths.size(); ++s) starts[s + 1] = starts[s] + table.lengths[s];
     std::vector<uint32_t> mism(n + 1), slice;
+    auto cover_depth = run.entry<decltype(&spd_cover_depth)>("spd_cover_depth");
     for (uint64_t i = 0; i < n;) {
         if (calls[i].seq >= table.lengths.size() || calls[i].pos >= table.lengths[calls[i].seq])
             fatal_error("a call lies outside the sequence table (sequence %u, position %llu)", calls[i].seq, (unsigned long long)calls[i].pos);
@@ -149,7 +98,7 @@ int call_main(int argc, char** argv) {
     if (std::fflush(out.f) != 0 || std::ferror(out.f)) fatal_error("write failed (disk full?): %s", out.path.c_str());
     out.close();
     std::fprintf(stderr, "[call] %llu reads, %llu mapped, %llu without a mapping, %llu calls (%.3f sec). results are saved in *.vcf\n",
-                 (unsigned long long)num_reads, (unsigned long long)num_mapped, (unsigned long long)(num_reads - num_mapped),
+                 (unsigned long long)counts.reads, (unsigned long long)counts.mapped, (unsigned long long)(counts.reads - counts.mapped),
                  (unsigned long long)n, std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count());
     return 0;
 }

@@ -52,10 +52,7 @@ int chain_main(int argc, char** argv) {
     parse_read_options(argc, argv, o, spumoni_chain_usage, true, m.shorts().c_str(), m.longs(),
                        [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni chain`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    o.ms = true;
+    imply_ms(o, "chain");
     validate_read_options(o);
     m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";

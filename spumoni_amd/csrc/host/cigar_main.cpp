@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../../include/spumoni_cigar.h"
+#include "cigar_text.hpp"
 #include "read_command.hpp"
 
 using namespace spumoni_host;
@@ -57,10 +58,7 @@ int cigar_main(int argc, char** argv) {
     parse_read_options(argc, argv, o, spumoni_cigar_usage, true, m.shorts().c_str(), m.longs(),
                        [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni cigar`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    o.ms = true;
+    imply_ms(o, "cigar");
     validate_read_options(o);
     m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";
@@ -80,27 +78,22 @@ int cigar_main(int argc, char** argv) {
     out.open(o.pattern_file + ".cigars", false);
     uint64_t num_reads = 0, num_aligned = 0, num_entries = 0;
     std::vector<spa_alignment> recs;
-    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
-    std::vector<uint32_t> ops;
-    static const char op_char[16] = {'?', 'I', 'D', 'N', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    BatchEntries entries;
     scan_reads(
         run, out,
         [&](ReadBatch& b) {
             recs.resize(b.take + 1);
-            op_offs.assign(b.take + 1, 0);
-            ops.clear();
+            entries.start(b.take);
             for_each_piece(b, [&](size_t q0, size_t q1) {
-                uint64_t n = 0;
-                if (cigar_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
-                                min_length, o.use_doc ? 1 : 0, &params, &fill, recs.data() + q0, nullptr, b.values.data() + q0,
-                                &n) != SPX_OK)
+                if (!entries.piece(
+                        q0, q1,
+                        [&](uint64_t* n) {
+                            return cigar_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0,
+                                               q1 - q0, min_length, o.use_doc ? 1 : 0, &params, &fill, recs.data() + q0, nullptr,
+                                               b.values.data() + q0, n);
+                        },
+                        [&](uint64_t* offs, uint32_t* ops) { return cigar_fetch(run.ix, offs, ops); }))
                     fatal_error("%s", spx_last_error());
-                const size_t at = ops.size();
-                ops.resize(at + n + 1);
-                piece_offs.resize(q1 - q0 + 1);
-                if (cigar_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
-                ops.resize(at + n);
-                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
             });
         },
         [&](const ReadBatch& b, size_t i) {
@@ -116,10 +109,9 @@ int cigar_main(int argc, char** argv) {
                          c.skipped);
             if (o.use_doc) std::fprintf(out.f, "\t%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
             std::fputc('\t', out.f);
-            if (op_offs[i] == op_offs[i + 1]) std::fputc('*', out.f);
-            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e) std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
+            write_cigar(out.f, entries, i, false, true);
             std::fputc('\n', out.f);
-            num_entries += op_offs[i + 1] - op_offs[i];
+            num_entries += entries.op_offs[i + 1] - entries.op_offs[i];
             num_aligned += aligned;
             num_reads++;
         });

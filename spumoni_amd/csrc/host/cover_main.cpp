@@ -6,9 +6,7 @@
 // everything has been fetched, so a run that fails leaves none.
 #include <unistd.h>
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -70,75 +68,29 @@ int cover_main(int argc, char** argv) {
                                min_depth = count_argument(arg);
                        });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni cover`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    if (o.use_promotions || o.use_dna_letters)
-        fatal_warning("-m / -a cannot be used with `spumoni cover`: digested coordinates cannot be turned back into bases. "
-                      "Map against an index built with -n -s.");
-    if (o.min_digest)
-        fatal_warning("`spumoni cover` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
-    o.ms = true;
+    imply_ms(o, "cover");
+    require_bases(o, "cover");
     validate_read_options(o);
     m.validate(o);
     if (min_depth > 4294967295ull) fatal_warning("the smallest depth (-D) must be between 0 and 4294967295.");
-    o.ref_file += ".fa";
-    const std::string table_path = o.ref_file + ".seqs";
-    if (!is_file(table_path))
-        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", table_path.c_str());
-    const SeqTable table = read_seq_table(table_path);
-    const std::vector<void*> entry =
-        device_entry_points("cover", {"spd_cover_add_batch", "spn_set_sequences", "spd_cover_reset", "spd_cover_summary",
-                                      "spd_cover_runs_begin", "spd_cover_runs_fetch"}, "the coverage kernels");
-    auto add_batch = reinterpret_cast<decltype(&spd_cover_add_batch)>(entry[0]);
-    auto set_sequences = reinterpret_cast<decltype(&spn_set_sequences)>(entry[1]);
-    auto reset = reinterpret_cast<decltype(&spd_cover_reset)>(entry[2]);
-    auto summary = reinterpret_cast<decltype(&spd_cover_summary)>(entry[3]);
-    auto runs_begin = reinterpret_cast<decltype(&spd_cover_runs_begin)>(entry[4]);
-    auto runs_fetch = reinterpret_cast<decltype(&spd_cover_runs_fetch)>(entry[5]);
-    ReadRun run;
-    open_read_run(o, 8u << 20, run);
-    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spd_cover_add_batch)
-    if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
-        fatal_error("%s: %s", table_path.c_str(), spx_last_error());
-    if (reset(run.ix) != SPX_OK) fatal_error("%s", spx_last_error());
-    const uint64_t min_length = m.min_length(o);
-    const spc_params params = m.chain();
-    const spa_params fill = m.fill();
-    const spe_params ends = m.ends();
-    std::fprintf(stderr, "[cover] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); %s\n",
-                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
-                 m.describe(min_length).c_str());
+    TableRun run;
+    open_table_run(o, m, "cover", {"spd_cover_add_batch", "spn_set_sequences", "spd_cover_reset", "spd_cover_summary", "spd_cover_runs_begin",
+                                   "spd_cover_runs_fetch"}, "the coverage kernels", "spd_cover_reset", run);
+    const SeqTable& table = run.table;
+    std::fprintf(stderr, "%s\n", run.loaded.c_str());
 
-    LinesFile none;  // (nothing is written per read)
-    none.keep_partial = false;
-    uint64_t num_reads = 0, num_mapped = 0;
-    std::vector<spn_mapping> maps;
-    scan_reads(
-        run, none,
-        [&](ReadBatch& b) {
-            maps.resize(b.take + 1);
-            for_each_piece(b, [&](size_t q0, size_t q1) {
-                if (add_batch(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
-                              o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0) != SPX_OK)
-                    fatal_error("%s", spx_last_error());
-                // (without digestion a read's values are its characters)
-                for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
-            });
-        },
-        [&](const ReadBatch&, size_t i) {
-            num_reads++;
-            num_mapped += maps[i].seq != SPN_UNMAPPED;
-        });
+    const ReadCounts counts = accumulate_reads(run, o, m, run.entry<decltype(&spd_cover_add_batch)>("spd_cover_add_batch"));
     // everything that can fail on the device comes before the first file
     std::vector<spd_seq_cover> cover(table.names.size());
-    if (summary(run.ix, cover.data(), cover.size()) != SPX_OK) fatal_error("%s", spx_last_error());
+    if (run.entry<decltype(&spd_cover_summary)>("spd_cover_summary")(run.ix, cover.data(), cover.size()) != SPX_OK)
+        fatal_error("%s", spx_last_error());
     std::vector<spd_run> runs;
     if (bedgraph) {
         uint64_t n = 0;
-        if (runs_begin(run.ix, (uint32_t)min_depth, &n) != SPX_OK) fatal_error("%s", spx_last_error());
+        if (run.entry<decltype(&spd_cover_runs_begin)>("spd_cover_runs_begin")(run.ix, (uint32_t)min_depth, &n) != SPX_OK)
+            fatal_error("%s", spx_last_error());
         runs.resize(n + 1);
-        if (runs_fetch(run.ix, runs.data()) != SPX_OK) fatal_error("%s", spx_last_error());
+        if (run.entry<decltype(&spd_cover_runs_fetch)>("spd_cover_runs_fetch")(run.ix, runs.data()) != SPX_OK) fatal_error("%s", spx_last_error());
         runs.resize(n);
     }
     uint64_t added = 0;
@@ -168,8 +120,8 @@ int cover_main(int argc, char** argv) {
     out.close();
     std::fprintf(stderr, "[cover] %llu reads, %llu mapped, %llu added to the coverage, %llu without a mapping (%.3f sec). results are saved in "
                  "*.cover%s\n",
-                 (unsigned long long)num_reads, (unsigned long long)num_mapped, (unsigned long long)added,
-                 (unsigned long long)(num_reads - num_mapped),
+                 (unsigned long long)counts.reads, (unsigned long long)counts.mapped, (unsigned long long)added,
+                 (unsigned long long)(counts.reads - counts.mapped),
                  std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t_start).count(), bedgraph ? " and *.bedgraph" : "");
     return 0;
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../../include/spumoni_extend.h"
+#include "cigar_text.hpp"
 #include "read_command.hpp"
 
 using namespace spumoni_host;
@@ -63,10 +64,7 @@ int extend_main(int argc, char** argv) {
     parse_read_options(argc, argv, o, spumoni_extend_usage, true, m.shorts().c_str(), m.longs(),
                        [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni extend`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    o.ms = true;
+    imply_ms(o, "extend");
     validate_read_options(o);
     m.validate(o);
     o.ref_file += o.use_promotions ? ".bin" : ".fa";
@@ -87,27 +85,22 @@ int extend_main(int argc, char** argv) {
     out.open(o.pattern_file + ".extended", false);
     uint64_t num_reads = 0, num_aligned = 0, num_entries = 0, num_clipped = 0;
     std::vector<spa_alignment> recs;
-    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
-    std::vector<uint32_t> ops;
-    static const char op_char[16] = {'?', 'I', 'D', 'N', 'S', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    BatchEntries entries;
     scan_reads(
         run, out,
         [&](ReadBatch& b) {
             recs.resize(b.take + 1);
-            op_offs.assign(b.take + 1, 0);
-            ops.clear();
+            entries.start(b.take);
             for_each_piece(b, [&](size_t q0, size_t q1) {
-                uint64_t n = 0;
-                if (extend_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
-                                 min_length, o.use_doc ? 1 : 0, &params, &fill, &ends, recs.data() + q0, nullptr,
-                                 b.values.data() + q0, nullptr, &n) != SPX_OK)
+                if (!entries.piece(
+                        q0, q1,
+                        [&](uint64_t* n) {
+                            return extend_begin(run.ix, run.digest_kind, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0,
+                                                q1 - q0, min_length, o.use_doc ? 1 : 0, &params, &fill, &ends, recs.data() + q0, nullptr,
+                                                b.values.data() + q0, nullptr, n);
+                        },
+                        [&](uint64_t* offs, uint32_t* ops) { return extend_fetch(run.ix, offs, ops); }))
                     fatal_error("%s", spx_last_error());
-                const size_t at = ops.size();
-                ops.resize(at + n + 1);
-                piece_offs.resize(q1 - q0 + 1);
-                if (extend_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
-                ops.resize(at + n);
-                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
             });
         },
         [&](const ReadBatch& b, size_t i) {
@@ -123,13 +116,11 @@ int extend_main(int argc, char** argv) {
                          c.skipped);
             if (o.use_doc) std::fprintf(out.f, "\t%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
             std::fprintf(out.f, "\t%llu\t", (unsigned long long)b.values[i]);
-            if (op_offs[i] == op_offs[i + 1]) std::fputc('*', out.f);
-            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e) {
-                std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
-                if ((ops[e] & 15) == SPE_OP_S) num_clipped += ops[e] >> 4;
-            }
+            write_cigar(out.f, entries, i, false, true);
             std::fputc('\n', out.f);
-            num_entries += op_offs[i + 1] - op_offs[i];
+            for (uint64_t e = entries.op_offs[i]; e < entries.op_offs[i + 1]; ++e)
+                if ((entries.ops[e] & 15) == SPE_OP_S) num_clipped += entries.ops[e] >> 4;
+            num_entries += entries.op_offs[i + 1] - entries.op_offs[i];
             num_aligned += aligned;
             num_reads++;
         });

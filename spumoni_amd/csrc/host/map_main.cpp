@@ -5,14 +5,11 @@
 // (same ids, same FASTA / FASTQ quirks as `run`), the MS index through the loaders `run` uses, and super-batches of
 // SPUMONI_SUPER_BATCH characters go through spn_map_begin / spn_map_fetch in calls of one piece each.  The driver is
 // read_command.cpp; a run that fails leaves no file.
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
 #include <vector>
 
 #include "../../../include/spumoni_map.h"
+#include "cigar_text.hpp"
 #include "read_command.hpp"
 
 using namespace spumoni_host;
@@ -64,66 +61,41 @@ int map_main(int argc, char** argv) {
     parse_read_options(argc, argv, o, spumoni_map_usage, true, m.shorts().c_str(), m.longs(),
                        [&](int c, const char* arg) { m.set(o, c, arg); });
     require_ref_and_pattern(o);
-    if (o.pml_requested)
-        fatal_warning("-P cannot be used with `spumoni map`: the anchors are read off matching statistics (-M is implied); "
-                      "PMLs have no pointers.");
-    if (o.use_promotions || o.use_dna_letters)
-        fatal_warning("-m / -a cannot be used with `spumoni map`: digested coordinates cannot be turned back into bases. "
-                      "Map against an index built with -n -s.");
-    if (o.min_digest)
-        fatal_warning("`spumoni map` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).");
-    o.ms = true;
+    imply_ms(o, "map");
+    require_bases(o, "map");
     validate_read_options(o);
     m.validate(o);
-    o.ref_file += ".fa";
-    const std::string table_path = o.ref_file + ".seqs";
-    if (!is_file(table_path))
-        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", table_path.c_str());
-    const SeqTable table = read_seq_table(table_path);
-    const std::vector<void*> entry =
-        device_entry_points("map", {"spn_set_sequences", "spn_map_begin", "spn_map_fetch"}, "the map kernels");
-    auto set_sequences = reinterpret_cast<decltype(&spn_set_sequences)>(entry[0]);
-    auto map_begin = reinterpret_cast<decltype(&spn_map_begin)>(entry[1]);
-    auto map_fetch = reinterpret_cast<decltype(&spn_map_fetch)>(entry[2]);
-    ReadRun run;
-    open_read_run(o, 8u << 20, run);
-    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per spn_map_begin)
-    if (set_sequences(run.ix, table.lengths.data(), table.lengths.size(), table.strands) != SPX_OK)
-        fatal_error("%s: %s", table_path.c_str(), spx_last_error());
-    const uint64_t min_length = m.min_length(o);
+    TableRun run;
+    open_table_run(o, m, "map", {"spn_set_sequences", "spn_map_begin", "spn_map_fetch"}, "the map kernels", nullptr, run);
+    const SeqTable& table = run.table;
+    auto map_begin = run.entry<decltype(&spn_map_begin)>("spn_map_begin");
+    auto map_fetch = run.entry<decltype(&spn_map_fetch)>("spn_map_fetch");
     const spc_params params = m.chain();
     const spa_params fill = m.fill();
     const spe_params ends = m.ends();
-    std::fprintf(stderr, "[map] index loaded (n = %llu, r = %llu), %llu sequences on %u strand(s); %s\n",
-                 (unsigned long long)run.set.n, (unsigned long long)run.set.r, (unsigned long long)table.names.size(), table.strands,
-                 m.describe(min_length).c_str());
+    std::fprintf(stderr, "%s\n", run.loaded.c_str());
 
     LinesFile out;
     out.open(o.pattern_file + ".paf", false);
     uint64_t num_reads = 0, num_mapped = 0, num_cut = 0, num_reverse = 0;
     std::vector<spn_mapping> maps;
     std::vector<spa_alignment> recs;
-    std::vector<uint64_t> op_offs, piece_offs;  // per read of the super-batch: where its entries start in `ops`
-    std::vector<uint32_t> ops;
-    static const char op_char[16] = {'?', 'I', 'D', 'N', 'S', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+    BatchEntries entries;
     scan_reads(
         run, out,
         [&](ReadBatch& b) {
             maps.resize(b.take + 1);
             recs.resize(b.take + 1);
-            op_offs.assign(b.take + 1, 0);
-            ops.clear();
+            entries.start(b.take);
             for_each_piece(b, [&](size_t q0, size_t q1) {
-                uint64_t n = 0;
-                if (map_begin(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, min_length,
-                              o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0, recs.data() + q0, &n) != SPX_OK)
+                if (!entries.piece(
+                        q0, q1,
+                        [&](uint64_t* n) {
+                            return map_begin(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0,
+                                             run.min_length, o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0, recs.data() + q0, n);
+                        },
+                        [&](uint64_t* offs, uint32_t* ops) { return map_fetch(run.ix, offs, ops); }))
                     fatal_error("%s", spx_last_error());
-                const size_t at = ops.size();
-                ops.resize(at + n + 1);
-                piece_offs.resize(q1 - q0 + 1);
-                if (map_fetch(run.ix, piece_offs.data(), ops.data() + at) != SPX_OK) fatal_error("%s", spx_last_error());
-                ops.resize(at + n);
-                for (size_t q = q0; q <= q1; ++q) op_offs[q] = at + piece_offs[q - q0];
                 // (without digestion a read's values are its characters)
                 for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
             });
@@ -140,8 +112,7 @@ int map_main(int argc, char** argv) {
                          m.matches, m.block, m.edits, c.anchors, m.cut);
             if (o.use_doc) std::fprintf(out.f, "\tdc:i:%lld", c.doc == SPC_NO_DOC ? -1ll : (long long)c.doc);
             std::fputs("\tcg:Z:", out.f);
-            for (uint64_t e = op_offs[i]; e < op_offs[i + 1]; ++e)
-                if ((ops[e] & 15) != SPE_OP_S) std::fprintf(out.f, "%u%c", ops[e] >> 4, op_char[ops[e] & 15]);
+            write_cigar(out.f, entries, i, true, false);
             std::fputc('\n', out.f);
             num_mapped++;
             num_cut += m.cut != 0;

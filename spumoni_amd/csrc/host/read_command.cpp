@@ -79,6 +79,21 @@ void require_ref_and_pattern(const ReadOptions& o) {
     if (o.ref_file == "" || o.pattern_file == "") fatal_warning("Both a reference file (-r) and pattern file (-p) must be provided.");
 }
 
+void imply_ms(ReadOptions& o, const char* command) {
+    if (o.pml_requested)
+        fatal_warning("-P cannot be used with `spumoni %s`: the anchors are read off matching statistics (-M is implied); "
+                      "PMLs have no pointers.", command);
+    o.ms = true;
+}
+
+void require_bases(const ReadOptions& o, const char* command) {
+    if (o.use_promotions || o.use_dna_letters)
+        fatal_warning("-m / -a cannot be used with `spumoni %s`: digested coordinates cannot be turned back into bases. "
+                      "Map against an index built with -n -s.", command);
+    if (o.min_digest)
+        fatal_warning("`spumoni %s` needs -n: digested coordinates cannot be turned back into bases (index built with -n -s).", command);
+}
+
 void validate_read_options(const ReadOptions& o) {
     const std::string base = o.ref_file + (o.use_promotions ? ".bin" : ".fa");
     if (!is_file(base)) fatal_error("The following path is not valid: %s (remember to only specify output prefix)", base.data());
@@ -212,6 +227,24 @@ std::string MapOptions::describe(uint64_t min_length) const {
     return s + ")";
 }
 
+std::vector<struct option> CallThresholds::longs(const std::vector<struct option>& own) const {
+    std::vector<struct option> t = {{"min-depth", required_argument, NULL, 'D'},
+                                    {"min-alt", required_argument, NULL, 'A'},
+                                    {"min-permille", required_argument, NULL, 'Q'}};
+    t.insert(t.end(), own.begin(), own.end());
+    return t;
+}
+bool CallThresholds::set(int c, const char* arg) {
+    if (c != 'D' && c != 'A' && c != 'Q') return false;
+    (c == 'D' ? min_depth : c == 'A' ? min_alt : min_permille) = count_argument(arg);
+    return true;
+}
+void CallThresholds::validate(const char* alt_what) const {
+    if (min_depth < 1 || min_depth > 4294967295ull) fatal_warning("the smallest depth (-D) must be between 1 and 4294967295.");
+    if (min_alt < 1 || min_alt > 4294967295ull) fatal_warning("%s (-A) must be between 1 and 4294967295.", alt_what);
+    if (min_permille > 1000) fatal_warning("the smallest share (-Q) must be between 0 and 1000 thousandths.");
+}
+
 // name<TAB>length<TAB>text_start<TAB>strands per line (spumoni_amd/map.py: read_seq_table)
 SeqTable read_seq_table(const std::string& path) {
     std::ifstream in(path, std::ios::binary);
@@ -247,6 +280,27 @@ SeqTable read_seq_table(const std::string& path) {
     }
     if (t.names.empty()) fatal_error("%s: no sequences", path.c_str());
     return t;
+}
+
+void open_table_run(ReadOptions& o, const MapOptions& m, const char* command, const std::vector<const char*>& names, const char* what,
+                    const char* reset_name, TableRun& run) {
+    o.ref_file += ".fa";
+    run.table_path = o.ref_file + ".seqs";
+    if (!is_file(run.table_path))
+        fatal_warning("the index has no sequence table (%s): build it with -s (spumoni build -n -s).", run.table_path.c_str());
+    run.table = read_seq_table(run.table_path);
+    run.names = names;
+    run.found = device_entry_points(command, names, what);
+    open_read_run(o, 8u << 20, run);
+    run.super_batch = std::min<size_t>(run.super_batch, 32u << 20);  // (one piece per call into the library)
+    const SeqTable& t = run.table;
+    if (run.entry<decltype(&spn_set_sequences)>("spn_set_sequences")(run.ix, t.lengths.data(), t.lengths.size(), t.strands) != SPX_OK)
+        fatal_error("%s: %s", run.table_path.c_str(), spx_last_error());
+    if (reset_name && run.entry<decltype(&spd_cover_reset)>(reset_name)(run.ix) != SPX_OK) fatal_error("%s", spx_last_error());
+    run.min_length = m.min_length(o);
+    run.loaded = "[" + std::string(command) + "] index loaded (n = " + std::to_string(run.set.n) + ", r = " + std::to_string(run.set.r) +
+                 "), " + std::to_string(t.names.size()) + " sequences on " + std::to_string(t.strands) + " strand(s); " +
+                 m.describe(run.min_length);
 }
 
 namespace {
@@ -349,6 +403,33 @@ void for_each_piece(const ReadBatch& b, const std::function<void(size_t, size_t)
         for (q1 = q0 + 1; q1 < b.take && q1 - q0 < (4u << 20) && b.offs[q1 + 1] - b.offs[q0] <= (32u << 20);) ++q1;
         call(q0, q1);
     }
+}
+
+ReadCounts accumulate_reads(TableRun& run, const ReadOptions& o, const MapOptions& m, decltype(&spd_cover_add_batch) add) {
+    const spc_params params = m.chain();
+    const spa_params fill = m.fill();
+    const spe_params ends = m.ends();
+    LinesFile none;  // (nothing is written per read)
+    none.keep_partial = false;
+    ReadCounts counts;
+    std::vector<spn_mapping> maps;
+    scan_reads(
+        run, none,
+        [&](ReadBatch& b) {
+            maps.resize(b.take + 1);
+            for_each_piece(b, [&](size_t q0, size_t q1) {
+                if (add(run.ix, 0, (uint32_t)o.k, (uint32_t)o.w, b.seqs.data(), b.offs.data() + q0, q1 - q0, run.min_length,
+                        o.use_doc ? 1 : 0, &params, &fill, &ends, maps.data() + q0) != SPX_OK)
+                    fatal_error("%s", spx_last_error());
+                // (without digestion a read's values are its characters)
+                for (size_t q = q0; q < q1; ++q) b.values[q] = b.offs[q + 1] - b.offs[q];
+            });
+        },
+        [&](const ReadBatch&, size_t i) {
+            counts.reads++;
+            counts.mapped += maps[i].seq != SPN_UNMAPPED;
+        });
+    return counts;
 }
 
 }  // namespace spumoni_host

@@ -1,21 +1,23 @@
-// read_command.hpp -- what `spumoni assign`, `mems`, `place` and the chain family (`chain` .. `call`) share: a command that
-// walks the reads of a FASTA / FASTQ file through one product of the device library and writes lines in input order.  The
-// shared options and their rules (`run`'s messages where the rule is the same, spumoni_main.cpp: validate), the look-up of
-// the product's entry points, the run's set-up -- one device (the first of SPUMONI_GPUS), the reads from reads.cpp, the
+// read_command.hpp -- what `spumoni assign`, `mems`, `place` and the chain family (`chain` .. `consensus`) share: a command
+// that walks the reads of a FASTA / FASTQ file through one product of the device library and writes lines in input order.
+// The shared options and their rules (`run`'s messages where the rule is the same, spumoni_main.cpp: validate), the look-up
+// of the product's entry points, the run's set-up -- one device (the first of SPUMONI_GPUS), the reads from reads.cpp, the
 // index through the loaders `run` uses --, the loop over super-batches of SPUMONI_SUPER_BATCH characters, and the output
-// file.  A command keeps its usage text, its own options and checks, its call into the library, its lines and its closing
-// line on stderr.
+// file; for `map`, `cover`, `call` and `consensus` the run bound to the sequence table, and for the last three the loop that
+// adds every super-batch to the genome's arrays.  A command keeps its usage text, its own options and checks, its call into
+// the library, its lines and its closing line on stderr.
 #pragma once
 #include <getopt.h>
 
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../../../include/spumoni_extend.h"
+#include "../../../include/spumoni_cover.h"
 #include "classify.hpp"
 #include "reads.hpp"
 
@@ -38,6 +40,10 @@ void parse_read_options(int argc, char** argv, ReadOptions& o, int (*usage)(), b
                         const std::vector<struct option>& extra_long, const std::function<void(int, const char*)>& extra);
 // the rules that do not depend on the command, in two parts: a command's own -M / -P rule stands between them and sets o.ms
 void require_ref_and_pattern(const ReadOptions& o);
+// `chain` .. `consensus` read their anchors off matching statistics: -P is refused, -M implied (o.ms set)
+void imply_ms(ReadOptions& o, const char* command);
+// `map` .. `consensus` report bases, not digested coordinates: -m / -a and a missing -n are refused
+void require_bases(const ReadOptions& o, const char* command);
 void validate_read_options(const ReadOptions& o);  // the paths, .doc with o.use_doc, the index files by o.ms, k, w, -m / -a
 // The command's entry points, looked up at run time and never linked: the binary must also load against libraries without
 // them (a CPU test double of the query boundary).  `what`: "the document votes".  Ends the process when one is missing or
@@ -67,8 +73,8 @@ struct LinesFile {
     void close();
 };
 
-// The mapping options of `chain` (-L -S -G -B -H), of `align` and `cigar` (FILL: -F on top) and of `extend`, `map`, `cover` and
-// `call` (EXTEND: -E -O -N -I on top of those), with their defaults: the option tables for parse_read_options, the setter
+// The mapping options of `chain` (-L -S -G -B -H), of `align` and `cigar` (FILL: -F on top) and of `extend`, `map`, `cover`,
+// `call` and `consensus` (EXTEND: -E -O -N -I on top of those), with their defaults: the option tables for parse_read_options, the setter
 // for its `extra` (false: not one of these), the range checks in the order of the options, the parameters for the library
 // and the "index loaded" line from "a match is an anchor" to the closing parenthesis.
 struct MapOptions {
@@ -90,13 +96,47 @@ struct MapOptions {
 // an option's count: a leading '-' is out of every range
 unsigned long long count_argument(const char* arg);
 
-// <prefix>.fa.seqs, the table `spumoni build -s` writes (`map`, `cover`): ends the process on a malformed table
+// The thresholds of `call` and `consensus` (-D -A -Q) in MapOptions' manner: the tables behind a command's own, the setter
+// (false: not one of these) and the range checks; `alt_what` is the command's wording of -A.
+struct CallThresholds {
+    unsigned long long min_depth = 2, min_alt = 2, min_permille = 500;
+    std::string shorts(const char* own = "") const { return std::string("D:A:Q:") + own; }
+    std::vector<struct option> longs(const std::vector<struct option>& own = {}) const;
+    bool set(int c, const char* arg);
+    void validate(const char* alt_what) const;
+};
+
+// <prefix>.fa.seqs, the table `spumoni build -s` writes (`map` .. `consensus`): ends the process on a malformed table
 struct SeqTable {
     std::vector<std::string> names;
     std::vector<uint64_t> lengths;
     uint32_t strands = 0;
 };
 SeqTable read_seq_table(const std::string& path);
+
+// The run of `map`, `cover`, `call` and `consensus`: bound to the index's sequence table, with the command's entry points
+// by name.  open_table_run puts .fa onto o.ref_file, refuses an index without a table and reads it -- both before the
+// entry points, so that they are reported on a machine without a device too --, looks the entry points up (`names` holds
+// spn_set_sequences; the first one is the one a library without them is said to lack), opens the run with super-batches of
+// one piece at the most, hands the table to the library and, where the command has one, calls `reset_name`'s entry point
+// on the handle (nullptr: none).  It leaves the anchors' minimum length and the head of the "index loaded" line:
+// "[command] index loaded (n = .., r = ..), N sequences on S strand(s); <m.describe>" -- the command appends its own clause.
+struct TableRun : ReadRun {
+    std::string table_path;
+    SeqTable table;
+    std::vector<const char*> names;
+    std::vector<void*> found;
+    uint64_t min_length = 0;
+    std::string loaded;
+    template <class F>
+    F entry(const char* name) const {
+        for (size_t i = 0; i < names.size(); ++i)
+            if (std::strcmp(names[i], name) == 0) return reinterpret_cast<F>(found[i]);
+        fatal_error("%s is not among the entry points this command looked up", name);
+    }
+};
+void open_table_run(ReadOptions& o, const MapOptions& m, const char* command, const std::vector<const char*>& names, const char* what,
+                    const char* reset_name, TableRun& run);
 
 struct ReadBatch {
     std::vector<ReadRec> recs;  // the first `take` are the batch
@@ -113,5 +153,12 @@ void scan_reads(ReadRun& run, LinesFile& out, const std::function<void(ReadBatch
 // A super-batch ends with the read that fills it, and short reads are many: `call(q0, q1)` for pieces [q0, q1) of at most
 // 4 Mi reads and 32 Mi characters, one piece of the staged walk each
 void for_each_piece(const ReadBatch& b, const std::function<void(size_t, size_t)>& call);
+
+// `cover`, `call` and `consensus`: every super-batch goes through `add` (spd_cover_add_batch or spl_call_add_batch, one
+// signature) in calls of one piece each, and nothing is written per read
+struct ReadCounts {
+    uint64_t reads = 0, mapped = 0;
+};
+ReadCounts accumulate_reads(TableRun& run, const ReadOptions& o, const MapOptions& m, decltype(&spd_cover_add_batch) add);
 
 }  // namespace spumoni_host

@@ -425,3 +425,23 @@ def test_no_device_fails_loudly_and_writes_nothing(built, tmp_path):
     assert r.returncode == 1
     assert "no usable gfx950 device" in r.stderr and "no CPU fallback" in r.stderr, r.stderr
     assert sorted(os.listdir(tmp_path)) == before
+
+
+def test_the_entries_and_their_text_under_the_sanitizers(tmp_path):
+    """The host code that gathers a super-batch's entries piece by piece and writes the CIGARs (spumoni_amd/csrc/host/
+    cigar_text.hpp) in a stand-alone program (tests/cigar_text_check.cpp) with the address and undefined-behaviour
+    sanitizers: five reads in two pieces, pieces and reads without entries, every op code, the longest run, and `map`'s
+    form without the clips.  The text is written out by hand here."""
+    exe = str(tmp_path / "cigar_text_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-o", exe, os.path.join(ROOT, "tests", "cigar_text_check.cpp")], check=True)
+    p = subprocess.run([exe, str(tmp_path / "out.txt")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "cigar text ok" in p.stdout, p.stdout + p.stderr
+    lines = (tmp_path / "out.txt").read_text().split("\n")
+    # two pieces (reads 0-2, reads 3-4): read 3's CIGAR is its own, not a slice of the first piece's entries
+    assert lines[:5] == ["3S10=1X2I", "*", "5=4D6N7=", "2S9=1S", "268435455=1="]
+    assert lines[5:10] == ["10=1X2I", "", "5=4D6N7=", "9=", "268435455=1="]  # `map`: no S, no *
+    assert lines[10:14] == ["1=", "*", "*", "2X"]  # a piece without entries between two with
+    assert lines[14:16] == ["*", "*"]
+    assert lines[16:18] == ["1?2I3D4N5S6?7?8=9X10?11?12?13?14?15?16?", "1?2I3D4N6?7?8=9X10?11?12?13?14?15?16?"]  # op codes 0 .. 15
+    assert lines[18:] == ["", ""]  # a read of clips only in `map`'s form, and the end of the file

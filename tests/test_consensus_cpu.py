@@ -273,6 +273,18 @@ def test_consensus_usage_without_arguments(built, tmp_path):
     (["-r", "ref", "-p", "reads.fa", "-n", "-J", "-1"], None, "the line width (-J) must be between 0 and 2147483647."),
     (["-r", "ref", "-p", "reads.fa", "-n"], None, "the index has no sequence table (ref.fa.seqs): build it with -s"),
     (["-r", "ref", "-p", "reads.fa", "-n"], b"\n", "ref.fa.seqs: no sequences"),
+    # the rest of `call`'s table (tests/test_call_cpu.py), with this command's wording of -A in full
+    (["-r", "ref", "-p", "reads.fa", "-n", "-m"], None, "-m / -a cannot be used with `spumoni consensus`"),
+    (["-r", "ref", "-p", "missing.fa", "-n"], None, "The following path is not valid: missing.fa"),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-L", "0"], None, "the minimum match length (-L) must be at least 1."),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-E", "4097"], None, "the largest extended end (-E) must be between 1 and 4096."),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-D", "4294967296"], None, "the smallest depth (-D) must be between 1 and 4294967295."),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-A", "0"], None,
+     "the fewest reads with a substituted letter or a deletion (-A) must be between 1 and 4294967295."),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-A", "-3"], None,
+     "the fewest reads with a substituted letter or a deletion (-A) must be between 1 and 4294967295."),
+    (["-r", "ref", "-p", "reads.fa", "-n", "-U", ">"], None, "the mask (-U) must be one byte other than a newline and '>'."),
+    (["-r", "ref", "-p", "reads.fa", "-n"], b"a\t5\t0\n", "ref.fa.seqs: line 1 is not name<TAB>length<TAB>text_start<TAB>strands"),
 ])
 def test_consensus_refusals_leave_no_file(built, tmp_path, args, table, message):
     _golden_index(tmp_path, table)
